@@ -2,8 +2,12 @@
 """Headline benchmark: real-time factor (audio-seconds / wall-seconds) of MDX-Net separation + RVC voice conversion
 on a 4-minute 44.1 kHz stereo track per GPU (BASELINE.json metric; configs of SURVEY 8d).
 
-  python bench.py --gpus N --steps K --warmup W [--config C3]
+  python bench.py --gpus N --steps K --warmup W [--config C3] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints one JSON line (value, ms_per_step, the per-stage wall split).  --full
+adds what the headline does not need: one instrumented step behind the timed region (roofline, stage table, profiled_step_ms) and,
+on one GPU, the CPU baseline.
 
 --config  C3 (default, the headline): MDX (1 model) -> separated vocals -> 44.1 kHz stereo to 16 kHz mono on the device ->
               VC.pipeline with rmvpe f0.  One "step" = one synthetic track of 240 s x N through both stages.
@@ -38,6 +42,7 @@ PEAK_F32_MFMA = 157.3   # TFLOP/s, MI355X_MICROARCH.md
 PEAK_BF16_MFMA = 2516.6  # TFLOP/s dense (16 x the fp32 MFMA rate, MI355X_MICROARCH.md "1/16 of BF16 MFMA")
 MFMA_PEAK = PEAK_F32_MFMA  # of the arithmetic in use: --precision bf16x3 spends three bf16 MFMAs per fp32 product -> bf16 / 3
 PEAK_HBM = 8000.0       # GB/s spec (6290 measured float4 copy)
+DUMP_MAX_ELEMS = 6 << 20  # --dump-outputs: float32 elements per array (two arrays stay under 64 MB)
 
 
 def build_models(device, config, n_mdx, tiny=False, preset="fp16", half=False):
@@ -200,6 +205,22 @@ def reference_cpu_record():
         return {}
 
 
+def dump_outputs(path, sep, out):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as float32 .npy files -- mdx_vocals, the separated
+    44.1 kHz stereo stem (last separation of the chain), and rvc_audio, VC.pipeline's int16 output (exact in float32; absent for C2).
+    An array of more than DUMP_MAX_ELEMS elements is stored as the same seeded sample of its flattened values in every run, so that
+    two builds given the same arguments can be compared element for element."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"mdx_vocals": sep.detach().float().cpu().numpy()}
+    if out is not None:
+        arrays["rvc_audio"] = np.asarray(out, dtype=np.float32)
+    for name, a in arrays.items():
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(1234).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def _free_port():
     import socket
     with socket.socket() as s:
@@ -233,8 +254,12 @@ def main():
     ap.add_argument("--preset", choices=["fp16", "fp32"], default="fp16",
                     help="RVC chunk geometry (src/rvc.py:76-93): fp16 = x_pad,x_query,x_center,x_max 3,10,60,65 (what main.py "
                          "selects, the headline), fp32 = 1,6,38,41.  Geometry only: the arithmetic is fp32 either way")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile-step", action="store_true", help="skip the extra instrumented step behind the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the instrumented step behind the timed region (roofline, "
+                         "stage table, profiled_step_ms, --conv-shapes) and the CPU baseline.  Off: set up, warm up, time the steps, "
+                         "dump the outputs if asked, print the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-profile-step", action="store_true", help="with --full: skip the extra instrumented step behind the timed region")
     ap.add_argument("--precision", choices=["fp32", "bf16x3", "f16"], default=None,
                     help="arithmetic of the conv / TDF GEMM family: fp32 MFMA (default, the headline) or the opt-in split precision "
                          "(bf16 hi + lo operands, 3 bf16 MFMAs per product, fp32 accumulation); f16: the reference's is_half mode on "
@@ -243,8 +268,16 @@ def main():
                          "default: $AICG_PRECISION or fp32")
     ap.add_argument("--track-seconds", type=float, default=None)
     ap.add_argument("--dump", type=str, default=None, help="write the last step's outputs (npz) for cross-checking runs")
-    ap.add_argument("--conv-shapes", type=str, default=None, help="write the instrumented step's per-layer-shape conv table (JSON)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32; arrays above %d M elements as a fixed "
+                         "seeded sample)" % (DUMP_MAX_ELEMS >> 20))
+    ap.add_argument("--conv-shapes", type=str, default=None, help="with --full: write the instrumented step's per-layer-shape conv "
+                                                                  "table (JSON)")
     args = ap.parse_args()
+    if args.conv_shapes and not args.full:
+        ap.error("--conv-shapes needs --full (the table comes from the instrumented step)")
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rc = self_launch(args)
     if rc is not None:
@@ -340,7 +373,7 @@ def main():
         # ~2 700 event records per step, kept OUT of the timed region; its own wall time is reported as profiled_step_ms ----
         prof = sprof = None
         prof_ms = None
-        if not args.no_profile_step and not emu:
+        if args.full and not args.no_profile_step and not emu:
             if rank == 0:
                 prof, sprof = ops.ConvProfile(), ops.StageProfile()
                 ops.conv_profile, ops.stage_profile = prof, sprof
@@ -463,9 +496,11 @@ def main():
                     json.dump(prof.by_shape(), f, indent=0)
         else:
             res["roofline"] = None
-        if world == 1 and not args.no_cpu_baseline and not emu:
+        if args.full and world == 1 and not args.no_cpu_baseline and not emu:
             with contextlib.redirect_stdout(sys.stderr):
                 res["cpu_baseline"] = dict(cpu_baseline(), **reference_cpu_record())
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, sep, out)
         if args.dump:
             np.savez_compressed(args.dump, sep=sep.cpu().numpy()[:, ::7], out=out if out is not None else np.zeros(1))
         sys.stdout.flush()

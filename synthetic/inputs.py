@@ -1,7 +1,23 @@
 """Seeded synthetic inputs shared by the golden generator, the parity tests and
 bench.py (all inputs are synthetic, seed 1234, generated in memory)."""
+import concurrent.futures
+import os
+
 import numpy as np
 import torch
+
+CHUNK = 1 << 18   # samples per task of _in_chunks
+
+
+def _in_chunks(n, fn):
+    """fn(0, n) for an element-wise fn(lo, hi) -> samples [lo, hi), evaluated in chunks on up to 16 threads (numpy's ufuncs release
+    the GIL): every sample goes through the same operations as in one pass, so the result is bit-identical.  bench.py's 4-minute
+    track costs ~190 sin passes over 10.6 M samples -- tens of seconds on one core."""
+    bounds = [(lo, min(n, lo + CHUNK)) for lo in range(0, n, CHUNK)]
+    if len(bounds) <= 1:
+        return fn(0, n)
+    with concurrent.futures.ThreadPoolExecutor(min(16, len(os.sched_getaffinity(0)), len(bounds))) as ex:
+        return np.concatenate(list(ex.map(lambda b: fn(*b), bounds)))
 
 
 def synth_inputs(cfg, T, seed):
@@ -40,17 +56,24 @@ def song_like(seconds, sr=44100, seed=1234):
     by construction) + -60 dBFS noise; stereo float32 (2, N), peak 0.95."""
     rng = np.random.default_rng(seed)
     n = int(round(seconds * sr))
-    t = np.arange(n) / sr
     voice = vocal_like(seconds, sr, seed).astype(np.float64)[:n]
-    acc = np.zeros(n)
+    partials = []
     for base in (130.81, 164.81, 196.0):
         for det in (0.997, 1.0, 1.004):
             f = base * det
             for k in range(1, 20):
                 if f * k > 6000:
                     break
-                acc += np.sin(2 * np.pi * f * k * t + rng.uniform(0, 6.28)) / k
-    acc *= 0.25 * (0.6 + 0.4 * np.sin(2 * np.pi * 0.5 * t))
+                partials.append((f, k, rng.uniform(0, 6.28)))
+
+    def accompaniment(lo, hi):
+        t = np.arange(lo, hi) / sr
+        acc = np.zeros(hi - lo)
+        for f, k, ph in partials:
+            acc += np.sin(2 * np.pi * f * k * t + ph) / k
+        acc *= 0.25 * (0.6 + 0.4 * np.sin(2 * np.pi * 0.5 * t))
+        return acc
+    acc = _in_chunks(n, accompaniment)
     d = 11
     left = voice + acc + 10 ** (-60 / 20) * rng.standard_normal(n)
     right = voice + np.concatenate([np.zeros(d), acc[:-d]]) + 10 ** (-60 / 20) * rng.standard_normal(n)

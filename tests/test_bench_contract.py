@@ -88,3 +88,56 @@ def test_stage_table_and_traffic_helpers():
     assert rows[2]["bound"] == "hbm" and abs(rows[2]["achieved"] - 350.0) < 1e-9
     t = b.pmc_traffic_per_launch()
     assert t is not None and t["fetch_x2"] > t["raw"] > 0 and t["source"].startswith("profiles/r0")
+
+
+def test_song_like_in_chunks_is_the_single_pass_signal(monkeypatch):
+    """bench.py's input track is generated in time chunks on a thread pool: bit for bit the single-pass signal (restated here), at
+    a chunk size that divides nothing."""
+    import numpy as np
+    from synthetic import inputs
+
+    def single_pass(seconds, sr, seed):
+        rng = np.random.default_rng(seed)
+        n = int(round(seconds * sr))
+        t = np.arange(n) / sr
+        voice = inputs.vocal_like(seconds, sr, seed).astype(np.float64)[:n]
+        acc = np.zeros(n)
+        for base in (130.81, 164.81, 196.0):
+            for det in (0.997, 1.0, 1.004):
+                f = base * det
+                for k in range(1, 20):
+                    if f * k > 6000:
+                        break
+                    acc += np.sin(2 * np.pi * f * k * t + rng.uniform(0, 6.28)) / k
+        acc *= 0.25 * (0.6 + 0.4 * np.sin(2 * np.pi * 0.5 * t))
+        left = voice + acc + 10 ** (-60 / 20) * rng.standard_normal(n)
+        right = voice + np.concatenate([np.zeros(11), acc[:-11]]) + 10 ** (-60 / 20) * rng.standard_normal(n)
+        out = np.stack([left, right])
+        return (0.95 * out / np.abs(out).max()).astype(np.float32)
+
+    monkeypatch.setattr(inputs, "CHUNK", 4099)
+    for seconds, sr, seed in ((2.3, 44100, 1234), (0.05, 44100, 7)):
+        got, want = inputs.song_like(seconds, sr, seed), single_pass(seconds, sr, seed)
+        assert got.dtype == np.float32 and np.array_equal(got.view(np.uint32), want.view(np.uint32))
+
+
+def test_dump_outputs_of_a_full_size_step(tmp_path):
+    """--dump-outputs at the headline's sizes (240 s: a 44.1 kHz stereo stem, 40 kHz int16 audio): float32, at most 64 MB in all,
+    large arrays as the same seeded sample on every call."""
+    import numpy as np
+    import torch
+    b = _bench()
+    sep = torch.randn(2, 240 * 44100)
+    out = (np.random.default_rng(0).standard_normal(240 * 40000) * 3000).astype(np.int16)
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), sep, out)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["mdx_vocals.npy", "rvc_audio.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64e6
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype == np.float32 and x.size == b.DUMP_MAX_ELEMS and np.array_equal(x, y)
+    v = np.load(tmp_path / "a" / "mdx_vocals.npy")
+    assert np.isin(v[:100], sep.numpy().reshape(-1)).all()                  # values of the output, not a resampling
+    b.dump_outputs(str(tmp_path / "c2"), torch.randn(2, 1000), None)        # C2: the MDX stage alone, stored whole
+    assert os.listdir(tmp_path / "c2") == ["mdx_vocals.npy"] and np.load(tmp_path / "c2" / "mdx_vocals.npy").shape == (2, 1000)

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -36,11 +37,16 @@ def test_plain_invocation_with_gpus_2_launches_two_ranks():
 
 
 @pytest.mark.timeout(600)
-def test_single_rank_line_and_world_size_mismatch():
-    r = _run(["--gpus", "1"])
+def test_single_rank_line_and_world_size_mismatch(tmp_path):
+    r = _run(["--gpus", "1", "--dump-outputs", str(tmp_path / "out")])
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][0])
     assert d["n_gpus"] == 1 and len(d["config"]["per_rank_seconds_per_step"]) == 1
+    # --dump-outputs: the last timed step's separated stem (stereo, 44.1 kHz) and converted audio (int16 values) as float32 arrays
+    sep, audio = np.load(tmp_path / "out" / "mdx_vocals.npy"), np.load(tmp_path / "out" / "rvc_audio.npy")
+    assert sorted(os.listdir(tmp_path / "out")) == ["mdx_vocals.npy", "rvc_audio.npy"]
+    assert sep.dtype == audio.dtype == np.float32 and sep.shape == (2, round(0.4 * 44100)) and audio.ndim == 1 and audio.size > 0
+    assert np.all(np.isfinite(sep)) and np.abs(sep).max() > 0 and np.array_equal(audio, np.round(audio))
     # a launcher that started a different number of ranks than --gpus asks for: no line, non-zero exit
     r = _run(["--gpus", "2"], {"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
     assert r.returncode != 0 and not r.stdout.strip() and "refusing" in r.stderr

@@ -4,7 +4,7 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out/verify; mkdir -p $O
 timeout 1500 python -m pytest tests -x -q -m gpu > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?"; tail -3 $O/pytest_gpu.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc=$?"; tail -1 $O/smoke.log
-timeout 900 python bench.py > $O/bench_c3_default.json 2> $O/bench_c3_default.err; echo "bench rc=$?"
+timeout 900 python bench.py --full > $O/bench_c3_default.json 2> $O/bench_c3_default.err; echo "bench rc=$?"
 python - <<'PY'
 import json
 s = json.loads(open("gpurun_out/verify/bench_c3_default.json").read().strip().splitlines()[-1])

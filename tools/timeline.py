@@ -1,6 +1,6 @@
 """Who runs when: the timed step of `bench.py` as a rocprofv3 kernel trace, per hardware queue.
 
-  (GPU box)  cd /tmp && rocprofv3 --kernel-trace --output-format csv -d <dir> -o bench -- python bench.py --steps 1 --warmup 1 --no-cpu-baseline
+  (GPU box)  cd /tmp && rocprofv3 --kernel-trace --output-format csv -d <dir> -o bench -- python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline
              python tools/timeline.py reduce <dir>/.../bench_kernel_trace.csv profiles/r05_kernel_trace_step.csv.gz
   (anywhere) python tools/timeline.py summary profiles/r05_kernel_trace_step.csv.gz > profiles/r05_timeline.json
 

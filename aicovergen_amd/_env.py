@@ -6,6 +6,9 @@ Supported in a user's process:
                                  synthesizer's LDS-DMA staged layers take fp16 operands, fp32 activations / accumulation (ops.mark_half; the f0
                                  models, SineGen, attention and MDX-Net stay fp32).  Without it .half() is a no-op and everything is fp32
     AICG_FORCE_COLLECTIVES=1     a one-rank process group runs every join through the real collectives (tests/test_rccl_one_rank.py)
+    AICG_DEVICE_POST=1           src/run_main.py puts src/compat first on sys.path: main.py's `pedalboard` / `pedalboard.io` / `pydub` imports
+                                 resolve to device stand-ins (aicovergen_amd.cover), so add_audio_effects and combine_audio run without those
+                                 libraries.  Unset, run_main.py leaves those imports to whatever is installed
 
 Everything else -- kernel-form selectors (AICG_WINOGRAD, AICG_WINOGRAD1D, AICG_W2D_*, AICG_GRU_*), schedule selectors (AICG_F0_SEGMENTS,
 AICG_OVERLAP_F0, AICG_OVERLAP_SYNTH, AICG_F0_PRIORITY, AICG_RB_STREAMS, AICG_MDX_BATCH) and reference-path selectors (AICG_FILTFILT,

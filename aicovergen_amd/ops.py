@@ -1008,6 +1008,68 @@ def to_int16(x, scale):
 
 
 # ---------------------------------------------------------------------------------------------------
+# Vocal effects chain and stem mix (csrc/fx.hip); parameters are derived in cover.py
+# ---------------------------------------------------------------------------------------------------
+FX_HPF, FX_COMP = 1, 2
+
+
+def fx_reverb_state_size(sr):
+    n = ctypes.c_int64(0)
+    _lib.call("aicg_fx_reverb_state_size", int(sr), ctypes.addressof(n))
+    return n.value
+
+
+def fx_dynamics(x, state_in, seg_len, warm, coefs, flags):
+    """x: (C, n) fp32.  coefs: (b0, b1, a1, cte_attack, cte_release, threshold, threshold_inv, ratio_inv).
+    Returns (y, state_out (C, 2))."""
+    assert x.dim() == 2 and x.is_contiguous() and x.dtype == torch.float32
+    C, n = x.shape
+    y = torch.empty_like(x)
+    st = torch.empty((C, 2), dtype=torch.float32, device=x.device)
+    assert state_in is None or (state_in.shape == st.shape and state_in.is_contiguous() and state_in.dtype == torch.float32)
+    _check(x, state_in)
+    _call("aicg_fx_dynamics", _ptr(x), _ptr(y), _ptr(state_in), _ptr(st), C, n, int(seg_len), int(warm),
+          *[float(v) for v in coefs], int(flags), _stream(x))
+    return y, st
+
+
+def fx_reverb(x, sr, state_in, seg_len, warm, coefs):
+    """x: (C, n) fp32.  coefs: (gain, damp, feedback, wet1, wet2, dry).  Returns (y, state_out (C, fx_reverb_state_size(sr)))."""
+    assert x.dim() == 2 and x.is_contiguous() and x.dtype == torch.float32
+    C, n = x.shape
+    y = torch.empty_like(x)
+    st = torch.empty((C, fx_reverb_state_size(sr)), dtype=torch.float32, device=x.device)
+    assert state_in is None or (state_in.shape == st.shape and state_in.is_contiguous() and state_in.dtype == torch.float32)
+    _check(x, state_in)
+    _call("aicg_fx_reverb", _ptr(x), _ptr(y), _ptr(state_in), _ptr(st), C, n, int(sr), int(seg_len), int(warm),
+          *[float(v) for v in coefs], _stream(x))
+    return y, st
+
+
+def fx_to_pcm16(x):
+    """(C, n) fp32 -> (n, C) int16, round to nearest of clamp(x, -1, 1) * 32767."""
+    assert x.dim() == 2 and x.is_contiguous() and x.dtype == torch.float32
+    C, n = x.shape
+    out = torch.empty((n, C), dtype=torch.int16, device=x.device)
+    _check(x)
+    _call("aicg_fx_to_pcm16", _ptr(x), _ptr(out), C, n, _stream(x))
+    return out
+
+
+def pcm16_mix(a, a_rate, a_gains, b, b_rate, b_gains, out_frames):
+    """a.overlay(b) in pydub's arithmetic.  a, b: (frames, channels) int16; *_gains: the two audioop.mul factors applied in order.
+    Returns (out_frames, max(channels)) int16 at max(a_rate, b_rate)."""
+    for t in (a, b):
+        assert t.dim() == 2 and t.is_contiguous() and t.dtype == torch.int16
+    ch = max(a.shape[1], b.shape[1])
+    out = torch.empty((int(out_frames), ch), dtype=torch.int16, device=a.device)
+    _check(a, b, out)
+    _call("aicg_pcm16_mix", _ptr(a), a.shape[1], int(a_rate), a.shape[0], float(a_gains[0]), float(a_gains[1]),
+          _ptr(b), b.shape[1], int(b_rate), b.shape[0], float(b_gains[0]), float(b_gains[1]), _ptr(out), int(out_frames), _stream(a))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------
 # CREPE helpers
 # ---------------------------------------------------------------------------------------------------
 def frame_normalize(frames):

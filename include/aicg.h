@@ -383,6 +383,40 @@ int aicg_ivf_scan8(const float* q, const float* vecs, const int64_t* list_off, c
 int aicg_index_mix(float* feats, const float* big, float* best_d, const int64_t* best_i, int rows, int dim, float rate,
                    int recompute, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Vocal effects chain and stem mix: the tail of song_cover_pipeline (src/main.py:206-233, called at :294 and :302).
+ * add_audio_effects runs pedalboard's HighpassFilter -> Compressor(ratio=4, threshold_db=-15) -> Reverb; combine_audio mixes with
+ * pydub.  Signals are fp32 (C, n) with C = 1 or 2 (channel-major); 16-bit PCM is interleaved [frames][C].
+ *
+ * The effects are recurrences.  A call is cut into segments of seg_len samples (seg_len <= 0 or >= n: one segment = the exact
+ * sequential recurrence); each segment restarts `warm` samples early from zero state and stores only its own samples.  A segment
+ * whose warm-up reaches the call's start begins there from state_in instead (NULL = zero state).  The last segment writes
+ * state_out, so that a signal processed in pieces equals one call.  state_in and state_out must not be the same buffer.
+ *
+ * aicg_fx_dynamics: flags bit 0 = first-order high-pass (y = b0 x + s; s = b1 x - a1 y), bit 1 = peak compressor
+ *   (env = |x| + (|x| > env ? cte_attack : cte_release) (env - |x|); gain = env < threshold ? 1 : powf(env threshold_inv,
+ *   ratio_inv - 1)), applied in that order per channel.  state: [C][2] = (high-pass state, envelope).
+ * aicg_fx_reverb: juce::Reverb (Freeverb) at sample_rate: 8 combs + 4 all-passes per channel, input gain `gain`, comb damping
+ *   `damp` and `feedback`; mono out = wet1 wet + dry x; stereo cross-mixes with wet2.  state: [C][aicg_fx_reverb_state_size]
+ *   floats (comb `last` values, delay-line positions, delay lines).  AICG_E_LDS when the delay lines exceed the 160 KiB LDS.
+ * aicg_fx_to_pcm16: out[f][c] = round-to-nearest(clamp(x[c][f], -1, 1) * 32767).
+ * aicg_pcm16_mix: a.overlay(b) as pydub computes it (audioop): each input gets apply_gain twice (audioop.mul by gain1, then by
+ *   gain2: floor, saturate), then both are brought to max(channels) (audioop.tostereo) and max(rate) (audioop.ratecv, fresh state);
+ *   out[0 .. out_frames) = a's converted frames (zero past their end) plus, saturating, b's converted frames (truncated to out).
+ *   The caller passes out_frames (pydub slices `a` to its length in whole milliseconds).
+ * ---------------------------------------------------------------------------------------------- */
+int aicg_fx_reverb_state_size(int sample_rate, int64_t* floats_per_channel);
+int aicg_fx_dynamics(const float* x, float* y, const float* state_in, float* state_out, int n_channels, int64_t n,
+                     int64_t seg_len, int64_t warm, float b0, float b1, float a1, float cte_attack, float cte_release,
+                     float threshold, float threshold_inv, float ratio_inv, int flags, void* stream);
+int aicg_fx_reverb(const float* x, float* y, const float* state_in, float* state_out, int n_channels, int64_t n,
+                   int sample_rate, int64_t seg_len, int64_t warm, float gain, float damp, float feedback, float wet1,
+                   float wet2, float dry, void* stream);
+int aicg_fx_to_pcm16(const float* x, int16_t* out, int n_channels, int64_t n, void* stream);
+int aicg_pcm16_mix(const int16_t* a, int a_channels, int a_rate, int64_t a_frames, double a_gain1, double a_gain2,
+                   const int16_t* b, int b_channels, int b_rate, int64_t b_frames, double b_gain1, double b_gain2,
+                   int16_t* out, int64_t out_frames, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,8 @@ Array level, on tensors where the bound library runs (device memory for the gfx9
 File level, with main.py's signatures and output names:
     add_audio_effects(audio_path, reverb_rm_size, reverb_wet, reverb_dry, reverb_damping) -> '<stem>_mixed.wav'
     combine_audio(audio_paths, output_path, main_gain, backup_gain, inst_gain, output_format)
+    pitch_shift(audio_path, pitch_change) -> '<stem>_p{pitch_change}.wav'   (main.py:138-147, `-pall N`)
+and on a signal: pitch_shift_signal(x, sr, semitones, offsets=None) -> (y, offsets): sox's `pitch` as WSOLA + resampling (csrc/pitch.hip)
 
 Parameters become coefficients here, in float32 the way JUCE derives them; the recurrences and the mix run in
 csrc/fx.hip.  The effects are computed in segments that restart from zero state `warm` samples early; the warm-up is chosen so that
@@ -233,6 +235,19 @@ def mix_stems(main_i16, main_sr, backup_i16, backup_sr, inst_i16, inst_sr, main_
     return overlay(first, r1, one, inst_i16, inst_sr, (db_to_float(-7), db_to_float(inst_gain)))
 
 
+def pitch_shift_signal(x, sr, semitones, offsets=None):
+    """sox `pitch` by `semitones` on a signal: time-stretch by d = 2^(semitones / 12) with WSOLA (pitch kept), then resample by d
+    back to the input's length (pitch moved).  x: (n,) or (C, n) float32 (C = 1 or 2).  offsets: the WSOLA offsets to use instead of
+    searching (int32, as returned), or None.  Returns (y with exactly x's frames, the offsets used); semitones == 0 returns a copy."""
+    x2, flat = _as_2d(x)
+    if semitones == 0:
+        return x.clone(), torch.zeros(0, dtype=torch.int32, device=x.device)
+    d = 2.0 ** (float(semitones) / 12.0)
+    z, offs = ops.tempo_wsola(x2, int(sr), 1.0 / d, offsets)
+    y = ops.resample_ratio(z, d, x2.shape[1])
+    return (y.view(-1) if flat else y), offs
+
+
 # ---------------------------------------------------------------------------------------------------
 # File level (main.py's signatures)
 # ---------------------------------------------------------------------------------------------------
@@ -276,6 +291,19 @@ def add_audio_effects(audio_path, reverb_rm_size, reverb_wet, reverb_dry, reverb
     xd = torch.from_numpy(x).to(_device())
     y, _ = vocal_effects(xd, sr, reverb_rm_size, reverb_wet, reverb_dry, reverb_damping)
     write_pcm16(output_path, ops.fx_to_pcm16(y).cpu().numpy(), sr)
+    return output_path
+
+
+def pitch_shift(audio_path, pitch_change):
+    """main.py:138-147: the file shifted by `pitch_change` semitones, written next to it as '<stem>_p{pitch_change}.wav' (16-bit PCM,
+    the input's rate and channel count); an existing output is returned as it is."""
+    output_path = f'{os.path.splitext(audio_path)[0]}_p{pitch_change}.wav'
+    if not os.path.exists(output_path):
+        x, sr = read_float(audio_path)
+        if x.shape[0] not in (1, 2):
+            raise NotImplementedError("%s: pitch_shift takes 1 or 2 channels, found %d" % (audio_path, x.shape[0]))
+        y, _ = pitch_shift_signal(torch.from_numpy(x).to(_device()), sr, pitch_change)
+        write_pcm16(output_path, ops.fx_to_pcm16(y).cpu().numpy(), sr)
     return output_path
 
 

@@ -1070,6 +1070,86 @@ def pcm16_mix(a, a_rate, a_gains, b, b_rate, b_gains, out_frames):
 
 
 # ---------------------------------------------------------------------------------------------------
+# Pitch shift of the backing stems (csrc/pitch.hip): WSOLA time-stretch, then resampling by an irrational ratio
+# ---------------------------------------------------------------------------------------------------
+def tempo_wsola_geometry(sr, tempo, n):
+    """(seg, search, ovl, skip, steps, n_out) in frames: sox's `tempo` music defaults at `sr` for the tempo factor `tempo`."""
+    g = (ctypes.c_int64 * 6)()
+    _lib.call("aicg_tempo_wsola_geometry", int(sr), float(tempo), int(n), ctypes.addressof(g))
+    return tuple(int(v) for v in g)
+
+
+def tempo_wsola(x, sr, tempo, offsets=None):
+    """x: (C, n) or (S, C, n) fp32 (S signals of one length, one workgroup each).  Duration is multiplied by 1 / tempo, pitch kept.
+    offsets: int32 (steps,) / (S, steps) to use instead of searching, or None.  Returns (y (.., C, n_out), offsets int32)."""
+    assert x.dim() in (2, 3) and x.is_contiguous() and x.dtype == torch.float32
+    S = 1 if x.dim() == 2 else x.shape[0]
+    C, n = x.shape[-2:]
+    steps, n_out = tempo_wsola_geometry(sr, tempo, n)[4:]
+    y = torch.empty(x.shape[:-1] + (n_out,), dtype=torch.float32, device=x.device)
+    offs = torch.zeros(x.shape[:-2] + (steps,), dtype=torch.int32, device=x.device)
+    if offsets is not None:
+        assert offsets.shape == offs.shape and offsets.dtype == torch.int32 and offsets.is_contiguous()
+    _check(x, offsets)
+    _call("aicg_tempo_wsola", _ptr(x), _ptr(y), _ptr(offs), _ptr(offsets), S, C, n, int(sr), float(tempo), _stream(x))
+    return y, offs
+
+
+# The resampling filter (DESIGN 8.1).  The output is stored as 16-bit PCM, so the response may deviate from the ideal one by at most
+# half a step of full scale, 2^-16 = -96.3 dB, in both bands; a Kaiser window has equal ripple in both, and A = 100 dB leaves the
+# window formulas' approximation some room (the achieved response is asserted in tests/test_cover_pitch.py).
+RESAMPLE_ATT_DB = 100.0
+RESAMPLE_PASS = 0.90       # passband edge as a share of the narrower Nyquist frequency; the stopband begins at that Nyquist
+RESAMPLE_PHASES = 1024     # table rows per input sample: linear interpolation between rows stays below 2^-18 (DESIGN 8.1)
+
+
+def resample_ratio_design(ratio):
+    """(fc, beta, half): cutoff in cycles per input sample (the middle of the transition band), Kaiser beta, and the filter's
+    half length in input samples, for y[m] = sum_t h(m ratio - t) x[t]."""
+    nu = min(1.0, 1.0 / float(ratio))
+    beta = 0.1102 * (RESAMPLE_ATT_DB - 8.7)
+    width = (1.0 - RESAMPLE_PASS) * nu / 2.0
+    half = int(math.ceil((RESAMPLE_ATT_DB - 7.95) / (2.285 * 2.0 * math.pi * width) / 2.0))
+    return (1.0 + RESAMPLE_PASS) / 2.0 * nu / 2.0, beta, half
+
+
+def resample_ratio_filter(tau, ratio):
+    """h(tau) in float64: 2 fc sinc(2 fc tau) I0(beta sqrt(1 - (tau / half)^2)) / I0(beta) inside (-half, half), 0 outside."""
+    fc, beta, half = resample_ratio_design(ratio)
+    tau = np.asarray(tau, np.float64)
+    u = 1.0 - (tau / half) ** 2
+    w = np.where(u > 0.0, np.i0(beta * np.sqrt(np.maximum(u, 0.0))) / np.i0(beta), 0.0)
+    return 2.0 * fc * np.sinc(2.0 * fc * tau) * w
+
+
+_ratio_tables = {}
+
+
+def resample_ratio_table(ratio):
+    """(table float32 (PHASES + 1, 2 half + 1), half): table[r][j + half] = h(r / PHASES + j), computed in float64."""
+    half = resample_ratio_design(ratio)[2]
+    r = np.arange(RESAMPLE_PHASES + 1, dtype=np.float64)[:, None] / RESAMPLE_PHASES
+    j = np.arange(-half, half + 1, dtype=np.float64)[None, :]
+    return resample_ratio_filter(r + j, ratio).astype(np.float32), half
+
+
+def resample_ratio(x, ratio, n_out):
+    """x: (C, n_in) or (S, C, n_in) fp32 -> (.., C, n_out): y[m] = sum_t h(m ratio - t) x[t], band-limited to the narrower Nyquist."""
+    assert x.dim() in (2, 3) and x.is_contiguous() and x.dtype == torch.float32
+    S = 1 if x.dim() == 2 else x.shape[0]
+    C, n_in = x.shape[-2:]
+    key = (float(ratio), str(x.device))
+    if key not in _ratio_tables:
+        t, half = resample_ratio_table(ratio)
+        _ratio_tables[key] = (torch.from_numpy(t).to(x.device), half)
+    table, half = _ratio_tables[key]
+    y = torch.empty(x.shape[:-1] + (int(n_out),), dtype=torch.float32, device=x.device)
+    _check(x, table)
+    _call("aicg_resample_ratio", _ptr(x), _ptr(y), S, C, n_in, int(n_out), float(ratio), _ptr(table), RESAMPLE_PHASES, half, _stream(x))
+    return y
+
+
+# ---------------------------------------------------------------------------------------------------
 # CREPE helpers
 # ---------------------------------------------------------------------------------------------------
 def frame_normalize(frames):

@@ -417,6 +417,30 @@ int aicg_pcm16_mix(const int16_t* a, int a_channels, int a_rate, int64_t a_frame
                    const int16_t* b, int b_channels, int b_rate, int64_t b_frames, double b_gain1, double b_gain2,
                    int16_t* out, int64_t out_frames, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Pitch shift of the backing stems: pitch_shift of song_cover_pipeline (src/main.py:138-147, called at :296-299 for `-pall N`),
+ * sox's `pitch` effect as its two stages.  Signals are fp32 [n_signals][C][n] with C = 1 or 2, all of one length.
+ *
+ * aicg_tempo_wsola: waveform-similarity overlap-add with sox's `tempo` defaults for music.  In frames at sample_rate:
+ *   seg = round(0.082 sr), search = round(0.01468 sr), ovl = max(round(0.012 sr), 16) & ~7, skip = round(tempo (seg - ovl));
+ *   the output has n_out = round(n / tempo) frames, made in steps = ceil(n_out / (seg - ovl)) steps of seg - ovl frames.
+ *   Step 0 copies the input's first seg - ovl frames (offset 0).  Step k >= 1 looks at p = k skip: the offset i_k in [0, search)
+ *   minimises sum_c sum_{j < ovl} (x[c][p + i + j] - o_k[c][j])^2 (channels summed, ties to the lowest i), where o_k is the ovl input
+ *   frames that follow what step k - 1 emitted; it emits the cross-fade o_k[j] (1 - j / ovl) + x[p + i_k + j] (j / ovl) for j < ovl
+ *   and x[p + i_k + j] for ovl <= j < seg - ovl.  Input past the end reads as zero.  offsets_out [n_signals][steps] receives the
+ *   i_k; offsets_in (same shape, or NULL) replaces the search: its values, clamped to [0, search), are used as the i_k.
+ *   One workgroup per signal.  AICG_E_LDS when the search window exceeds the 160 KiB LDS.
+ * aicg_tempo_wsola_geometry: geom[0..6) = seg, search, ovl, skip, steps, n_out for the same arguments.
+ * aicg_resample_ratio: y[c][m] = sum_t h(m ratio - t) x[c][t] for m < n_out, x zero outside [0, n_in).  h is given as the table
+ *   table[r][j + half_taps] = h(r / phases + j), r = 0 .. phases (phases + 1 rows of 2 half_taps + 1 floats), h = 0 outside
+ *   (-half_taps, half_taps); values between rows are interpolated linearly.  Phase, interpolation and sum are float64.
+ * ---------------------------------------------------------------------------------------------- */
+int aicg_tempo_wsola_geometry(int sample_rate, double tempo, int64_t n, int64_t* geom);
+int aicg_tempo_wsola(const float* x, float* y, int* offsets_out, const int* offsets_in, int n_signals, int n_channels, int64_t n,
+                     int sample_rate, double tempo, void* stream);
+int aicg_resample_ratio(const float* x, float* y, int n_signals, int n_channels, int64_t n_in, int64_t n_out, double ratio,
+                        const float* table, int phases, int half_taps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

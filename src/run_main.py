@@ -6,8 +6,8 @@ rmvpe, my_utils, infer_pack.models) resolving to the MI355X implementation.
 `python src/main.py` puts the reference's src/ first on sys.path; runpy does the same for the target script, so this
 directory is inserted after the target's own directory has been computed but ahead of it in the search order.
 
-With AICG_DEVICE_POST=1 the stand-ins under src/compat (pedalboard, pedalboard.io, pydub) come first as well, so that main.py's
-add_audio_effects and combine_audio run on the device (aicovergen_amd.cover); without it those imports are left alone."""
+With AICG_DEVICE_POST=1 the stand-ins under src/compat (pedalboard, pedalboard.io, pydub, sox) come first as well, so that main.py's
+pitch_shift, add_audio_effects and combine_audio run on the device (aicovergen_amd.cover); without it those imports are left alone."""
 import os
 import runpy
 import sys

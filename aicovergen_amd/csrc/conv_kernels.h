@@ -1237,9 +1237,11 @@ inline int choose_tile_width(const ConvArgs& p, int BN) {
     return best;
 }
 
-template <int BM, int BN, int WM, int WN>
-static int launch_conv(ConvArgs& p, hipStream_t stream) {
-    // output patch: TW (power of two) columns x TH rows = BN positions
+// Patch geometry of one launch on BN-position tiles, shared by every launcher of the implicit-GEMM family (they differ in the three
+// numbers passed in): the output patch is TW (power of two) columns x TH rows = BN positions; a K chunk holds as many channels --
+// at least min_bkc, never (much) more than the layer has -- as keep the staged input patch within patch_budget floats; a weight
+// stage takes as few, equally sized groups of taps per chunk as fit stage_rows rows.  Fills TW .. div_twp and nothing else.
+inline void conv_patch_geometry(ConvArgs& p, int BN, int min_bkc, int patch_budget, int stage_rows) {
     p.TW = choose_tile_width(p, BN);
     p.TWlog2 = ilog2(p.TW);
     p.TH = BN / p.TW;
@@ -1249,14 +1251,11 @@ static int launch_conv(ConvArgs& p, hipStream_t stream) {
     p.CHS = p.TH_in * p.TWp;
     p.tiles_w = idiv_up(p.Wo, p.TW);
     p.tiles_h = idiv_up(p.Ho, p.TH);
-    // channels per K chunk: as many as keep the staged patch within 8 prefetch registers per thread (2048 floats)
-    // and a weight stage within KSTAGE rows; never (much) more than the layer has
     p.BKC = 32;
-    constexpr int XRMAX = (WM * WN == 8) ? 8 : 12;  // 8-wave tiles run at 4 waves/SIMD: 128 registers per lane
-    while (p.BKC > 2 && (p.BKC * p.CHS > XRMAX * 64 * WM * WN || p.BKC >= 2 * p.Cin_g)) p.BKC >>= 1;
+    while (p.BKC > min_bkc && (p.BKC * p.CHS > patch_budget || p.BKC >= 2 * p.Cin_g)) p.BKC >>= 1;
     p.BKClog2 = ilog2(p.BKC);
-    {   // taps per weight stage: as few, equally sized stages per chunk as fit KSTAGE rows
-        const int cap = imax(1, KSTAGE / p.BKC);
+    {   // taps per weight stage
+        const int cap = imax(1, stage_rows / p.BKC);
         const int nstg = idiv_up(p.taps, cap);
         p.TT = idiv_up(p.taps, nstg);
     }
@@ -1265,6 +1264,13 @@ static int launch_conv(ConvArgs& p, hipStream_t stream) {
     p.xs_elems = (p.xs_total + 3) & ~3;
     p.div_chs = div_mul(p.CHS);
     p.div_twp = div_mul(p.TWp);
+}
+
+template <int BM, int BN, int WM, int WN>
+static int launch_conv(ConvArgs& p, hipStream_t stream) {
+    // patch budget: 8 prefetch registers per thread on the 8-wave tiles (they run at 4 waves/SIMD: 128 registers per lane), 12 on the others
+    constexpr int XRMAX = (WM * WN == 8) ? 8 : 12;
+    conv_patch_geometry(p, BN, 2, XRMAX * 64 * WM * WN, KSTAGE);
     // + 2 weight rows of slack: the MFMA loop's last (discarded) fragment prefetch reads one k-step past the stage
     const size_t lds = (size_t)(p.xs_elems + (KSTAGE + 2) * BM) * sizeof(float);
     const int xr = idiv_up(p.xs_total, 64 * WM * WN);
@@ -1279,28 +1285,7 @@ static int launch_conv(ConvArgs& p, hipStream_t stream) {
 // wave-specialised launch: returns 1 when the configuration does not fit (caller uses conv_mfma_kernel)
 template <int BM, int BN, int WM, int WN, int KS>
 static int launch_conv_ws(ConvArgs& p, hipStream_t stream) {
-    p.TW = choose_tile_width(p, BN);
-    p.TWlog2 = ilog2(p.TW);
-    p.TH = BN / p.TW;
-    p.TH_in = (p.TH - 1) * p.sh + (p.KH - 1) * p.dh + 1;
-    p.TW_in = (p.TW - 1) * p.sw + (p.KW - 1) * p.dw + 1;
-    p.TWp = p.TW_in | 1;
-    p.CHS = p.TH_in * p.TWp;
-    p.tiles_w = idiv_up(p.Wo, p.TW);
-    p.tiles_h = idiv_up(p.Ho, p.TH);
-    p.BKC = 32;
-    while (p.BKC > 2 && (p.BKC * p.CHS > 12 * 256 || p.BKC >= 2 * p.Cin_g)) p.BKC >>= 1;
-    p.BKClog2 = ilog2(p.BKC);
-    {
-        const int cap = imax(1, KS / p.BKC);
-        const int nstg = idiv_up(p.taps, cap);
-        p.TT = idiv_up(p.taps, nstg);
-    }
-    p.nchunk = idiv_up(p.Cin_g, p.BKC);
-    p.xs_total = p.BKC * p.CHS;
-    p.xs_elems = (p.xs_total + 3) & ~3;
-    p.div_chs = div_mul(p.CHS);
-    p.div_twp = div_mul(p.TWp);
+    conv_patch_geometry(p, BN, 2, 12 * 256, KS);
     const int xr = idiv_up(p.xs_total, 256) <= 8 ? 8 : 12;
     const size_t lds = (size_t)(2 * xr * 256 + 2 * WsGeom<BM, KS>::WS_ELEMS) * sizeof(float);
     // hoisted producer offsets are 32-bit byte offsets below kBufOob: one channel chunk of the input / one group of packed
@@ -1340,28 +1325,7 @@ static int launch_conv_ws(ConvArgs& p, hipStream_t stream) {
 template <int BM>
 static int launch_conv16(ConvArgs& p, hipStream_t stream) {
     constexpr int BN = 256;
-    p.TW = choose_tile_width(p, BN);
-    p.TWlog2 = ilog2(p.TW);
-    p.TH = BN / p.TW;
-    p.TH_in = (p.TH - 1) * p.sh + (p.KH - 1) * p.dh + 1;
-    p.TW_in = (p.TW - 1) * p.sw + (p.KW - 1) * p.dw + 1;
-    p.TWp = p.TW_in | 1;
-    p.CHS = p.TH_in * p.TWp;
-    p.tiles_w = idiv_up(p.Wo, p.TW);
-    p.tiles_h = idiv_up(p.Ho, p.TH);
-    p.BKC = 32;
-    while (p.BKC > 4 && (p.BKC * p.CHS > 12 * 256 || p.BKC >= 2 * p.Cin_g)) p.BKC >>= 1;
-    p.BKClog2 = ilog2(p.BKC);
-    {
-        const int cap = imax(1, KSTAGE / p.BKC);
-        const int nstg = idiv_up(p.taps, cap);
-        p.TT = idiv_up(p.taps, nstg);
-    }
-    p.nchunk = idiv_up(p.Cin_g, p.BKC);
-    p.xs_total = p.BKC * p.CHS;
-    p.xs_elems = (p.xs_total + 3) & ~3;
-    p.div_chs = div_mul(p.CHS);
-    p.div_twp = div_mul(p.TWp);
+    conv_patch_geometry(p, BN, 4, 12 * 256, KSTAGE);
     const size_t lds = (size_t)(p.xs_elems + (KSTAGE + 4) * BM) * sizeof(float);
     const int xr = idiv_up(p.xs_total, 256);
     if (lds > 160 * 1024 || xr > 12 || (long)p.xs_total * p.CHS >= (1L << 32)) return 1;  // caller falls back to the 32x32 kernel

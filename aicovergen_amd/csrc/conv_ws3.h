@@ -316,28 +316,7 @@ __global__ void __launch_bounds__(64 * (WM * WN + 4), (WM * WN == 4 ? 4 : 3)) co
 template <int BM, int BN, int WM, int WN, int KS>
 static int launch_conv_ws3(ConvArgs& p, hipStream_t stream) {
     if (p.Cin_g < 8 || !p.w3) return 1;
-    p.TW = choose_tile_width(p, BN);
-    p.TWlog2 = ilog2(p.TW);
-    p.TH = BN / p.TW;
-    p.TH_in = (p.TH - 1) * p.sh + (p.KH - 1) * p.dh + 1;
-    p.TW_in = (p.TW - 1) * p.sw + (p.KW - 1) * p.dw + 1;
-    p.TWp = p.TW_in | 1;
-    p.CHS = p.TH_in * p.TWp;
-    p.tiles_w = idiv_up(p.Wo, p.TW);
-    p.tiles_h = idiv_up(p.Ho, p.TH);
-    p.BKC = 32;
-    while (p.BKC > 8 && (p.BKC * p.CHS > 12 * 256 || p.BKC >= 2 * p.Cin_g)) p.BKC >>= 1;
-    p.BKClog2 = ilog2(p.BKC);
-    {
-        const int cap = imax(1, KS / p.BKC);
-        const int nstg = idiv_up(p.taps, cap);
-        p.TT = idiv_up(p.taps, nstg);
-    }
-    p.nchunk = idiv_up(p.Cin_g, p.BKC);
-    p.xs_total = p.BKC * p.CHS;
-    p.xs_elems = (p.xs_total + 3) & ~3;
-    p.div_chs = div_mul(p.CHS);
-    p.div_twp = div_mul(p.TWp);
+    conv_patch_geometry(p, BN, 8, 12 * 256, KS);
     if (p.xs_total > 12 * 256) return 1;
     const int xq = idiv_up(p.xs_total / 4, 256) <= 2 ? 2 : 3;
     const size_t lds = (size_t)(2 * xq * 256 * 4 + 2 * Ws3Geom<BM, KS>::WS_ELEMS) * sizeof(float);
@@ -473,30 +452,9 @@ template <int BM>
 static int launch_conv_ws3m16(ConvArgs& p, hipStream_t stream) {
     constexpr int BN = 256, KS = KSTAGE;
     if (p.Cin_g < 16 || !p.w3) return 1;
-    p.TW = choose_tile_width(p, BN);
-    p.TWlog2 = ilog2(p.TW);
-    p.TH = BN / p.TW;
-    p.TH_in = (p.TH - 1) * p.sh + (p.KH - 1) * p.dh + 1;
-    p.TW_in = (p.TW - 1) * p.sw + (p.KW - 1) * p.dw + 1;
-    p.TWp = p.TW_in | 1;
-    p.CHS = p.TH_in * p.TWp;
-    p.tiles_w = idiv_up(p.Wo, p.TW);
-    p.tiles_h = idiv_up(p.Ho, p.TH);
-    p.BKC = 32;
     // patch budget: 6 quads per producer thread (24 KB per buffer) -- a 256-position 2-D tile with its halo is ~350 positions
     // and a k-step group needs 16 channels of it
-    while (p.BKC > 16 && (p.BKC * p.CHS > 24 * 256 || p.BKC >= 2 * p.Cin_g)) p.BKC >>= 1;
-    p.BKClog2 = ilog2(p.BKC);
-    {
-        const int cap = imax(1, KS / p.BKC);
-        const int nstg = idiv_up(p.taps, cap);
-        p.TT = idiv_up(p.taps, nstg);
-    }
-    p.nchunk = idiv_up(p.Cin_g, p.BKC);
-    p.xs_total = p.BKC * p.CHS;
-    p.xs_elems = (p.xs_total + 3) & ~3;
-    p.div_chs = div_mul(p.CHS);
-    p.div_twp = div_mul(p.TWp);
+    conv_patch_geometry(p, BN, 16, 24 * 256, KS);
     if (p.xs_total > 24 * 256) return 1;
     const int xq = idiv_up(p.xs_total / 4, 256) <= 3 ? 3 : 6;
     const size_t lds = (size_t)(2 * xq * 256 * 4 + 2 * Ws3Geom<BM, KS>::WS_ELEMS) * sizeof(float);
@@ -619,28 +577,7 @@ static int launch_conv_ws3m16h(ConvArgs& p, hipStream_t stream) {
     //  thread at 64 rows, two at 72 -- measured slower with it and keeps 64)
     constexpr int BN = 256, KS = BM == 48 ? 72 : 64;
     if (p.Cin_g < 8 || !p.w3) return 1;
-    p.TW = choose_tile_width(p, BN);
-    p.TWlog2 = ilog2(p.TW);
-    p.TH = BN / p.TW;
-    p.TH_in = (p.TH - 1) * p.sh + (p.KH - 1) * p.dh + 1;
-    p.TW_in = (p.TW - 1) * p.sw + (p.KW - 1) * p.dw + 1;
-    p.TWp = p.TW_in | 1;
-    p.CHS = p.TH_in * p.TWp;
-    p.tiles_w = idiv_up(p.Wo, p.TW);
-    p.tiles_h = idiv_up(p.Ho, p.TH);
-    p.BKC = 32;
-    while (p.BKC > 8 && (p.BKC * p.CHS > 12 * 256 || p.BKC >= 2 * p.Cin_g)) p.BKC >>= 1;
-    p.BKClog2 = ilog2(p.BKC);
-    {
-        const int cap = imax(1, KS / p.BKC);
-        const int nstg = idiv_up(p.taps, cap);
-        p.TT = idiv_up(p.taps, nstg);
-    }
-    p.nchunk = idiv_up(p.Cin_g, p.BKC);
-    p.xs_total = p.BKC * p.CHS;
-    p.xs_elems = (p.xs_total + 3) & ~3;
-    p.div_chs = div_mul(p.CHS);
-    p.div_twp = div_mul(p.TWp);
+    conv_patch_geometry(p, BN, 8, 12 * 256, KS);
     if (p.xs_total > 12 * 256) return 1;
     const int xq = idiv_up(p.xs_total / 4, 256) <= 2 ? 2 : 3;
     const size_t lds = (size_t)(2 * xq * 256 * 4 + 2 * Ws3Geom<BM, KS>::WS_ELEMS) * sizeof(float);

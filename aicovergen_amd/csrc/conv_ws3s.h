@@ -245,28 +245,7 @@ __global__ void __launch_bounds__(64 * (WM * WN + 4), (WM * WN == 4 ? 4 : 3)) co
 template <int BM, int BN, int WM, int WN, int KS>
 static int launch_conv_ws3s(ConvArgs& p, hipStream_t stream) {
     if (p.Cin_g < 16 || !p.wsplit) return 1;
-    p.TW = choose_tile_width(p, BN);
-    p.TWlog2 = ilog2(p.TW);
-    p.TH = BN / p.TW;
-    p.TH_in = (p.TH - 1) * p.sh + (p.KH - 1) * p.dh + 1;
-    p.TW_in = (p.TW - 1) * p.sw + (p.KW - 1) * p.dw + 1;
-    p.TWp = p.TW_in | 1;
-    p.CHS = p.TH_in * p.TWp;
-    p.tiles_w = idiv_up(p.Wo, p.TW);
-    p.tiles_h = idiv_up(p.Ho, p.TH);
-    p.BKC = 32;
-    while (p.BKC > 16 && (p.BKC * p.CHS > 16 * 256 || p.BKC >= 2 * p.Cin_g)) p.BKC >>= 1;
-    p.BKClog2 = ilog2(p.BKC);
-    {
-        const int cap = imax(1, KS / p.BKC);
-        const int nstg = idiv_up(p.taps, cap);
-        p.TT = idiv_up(p.taps, nstg);
-    }
-    p.nchunk = idiv_up(p.Cin_g, p.BKC);
-    p.xs_total = p.BKC * p.CHS;
-    p.xs_elems = (p.xs_total + 3) & ~3;
-    p.div_chs = div_mul(p.CHS);
-    p.div_twp = div_mul(p.TWp);
+    conv_patch_geometry(p, BN, 16, 16 * 256, KS);
     if (p.xs_total > 24 * 256) return 1;   // <= 3 items of 8 channels per producer thread (3 only for 16-channel chunks of wide patches)
     const int xi = imax(1, idiv_up(p.xs_total / 8, 256));
     const size_t lds = (size_t)(2 * 2 * xi * 256 * 4 + 2 * Ws3Geom<BM, KS>::WS_ELEMS) * sizeof(float);

@@ -10,14 +10,15 @@ upsample / protect blend and the whole synthesizer.  Host numpy keeps the O(N) p
 import functools
 import os
 import traceback
+import warnings
 from time import time as ttime
 
 import numpy as np
 import torch
-from . import _env
 import torch.nn.functional as F
 from scipy import signal
 
+from . import _env
 from . import ops
 from . import dist as adist
 
@@ -80,6 +81,73 @@ def _bracket_pipeline(fn):
             self._in_pipeline = False
             self._group = None
     return wrapper
+
+
+class _Call:
+    """One VC.pipeline call: the arguments its chunk routine needs (model, net_g, sid, index, big_npy, index_rate, version, protect, if_f0,
+    noise_fn, times, f0_args = get_f0's positional arguments), the track (audio_pad, bounds, p_len, mine = this rank's chunks), the schedule
+    VC._schedule chose ("serial" | "one_launch" | "progressive", nseg, two_streams), and what the schedule's steps hand to each other."""
+
+    def __init__(self, **args):
+        self.__dict__.update(args)
+        self.overlap, self.progressive = self.schedule != "serial", self.schedule == "progressive"
+        self.pitch = self.pitchf = self.main = self.side = self.enc = None
+        self.pad_dev = None       # overlapped schedules: the padded track as float32 on the device
+        self.feats_of, self.pieces = {}, {}
+        self.fronts = {}          # two streams: chunk -> (state of its queued encoder half, event, inputs kept alive)
+        self.gru_seg, self.f0_bad = None, False    # progressive f0: the recurrence's handle (its exchange-timeout word is polled between chunks)
+        self.marks, self.cover = [], (self.p_len, 0)    # progressive f0: (first frame, end frame, event) -- the frame range whose pitch exists once the event has fired
+        self.tf0 = self.t2 = self.f0_wait = 0.0    # side stream forked; features (and, unless progressive, f0) exist; of that, waiting for f0
+
+    def noise(self, ci):
+        return self.noise_fn(ci, *self.bounds[ci]) if self.noise_fn is not None else None
+
+    def frames_of(self, ci):
+        s, e = self.bounds[ci]
+        return s // self.window, (self.p_len if ci == len(self.bounds) - 1 else (e - self.window) // self.window)
+
+    def chunk_pitch(self, ci):
+        if self.if_f0 != 1:
+            return None, None
+        fa, fb = self.frames_of(ci)
+        return self.pitch[:, fa:fb], self.pitchf[:, fa:fb]
+
+    def publish(self, lo, hi, f0bak, coarse):
+        """Progressive f0: write the pitch of frames [lo, hi), queued on `side`; with it the covered range grows to both sides."""
+        hi = min(hi, self.p_len)
+        if lo < hi:
+            self.pitch[0, lo:hi] = coarse[: hi - lo]
+            self.pitchf[0, lo:hi] = f0bak[: hi - lo].float()
+        self.cover = (min(self.cover[0], lo), max(self.cover[1], hi))
+        ev = torch.cuda.Event() if self.on_gpu else _HostEvent()
+        ev.record(self.side)
+        self.marks.append(self.cover + (ev,))
+
+    def mark_of(self, ci):
+        """Index of the first mark whose range covers the chunk's frames."""
+        fa, fb = self.frames_of(ci)
+        for m, (lo, hi, _) in enumerate(self.marks):
+            if lo <= fa and min(fb, self.p_len) <= hi:
+                return m
+        return len(self.marks) - 1
+
+    def order(self):
+        """This rank's chunks in the order the loop takes them: as their pitch is published (middle-out) under the progressive schedule
+        -- asked once the whole recurrence has been queued -- and first to last otherwise."""
+        return sorted(self.mine, key=lambda ci: (self.mark_of(ci), ci)) if self.progressive else list(self.mine)
+
+    def wait_pitch(self, stream, ci):
+        if self.progressive:
+            stream.wait_event(self.marks[self.mark_of(ci)][2])      # this chunk's pitch frames exist
+
+    def drain(self):
+        """The chunk's work is done (progressive: without waiting for the f0 stream's remaining segments)."""
+        if not self.on_gpu:
+            return
+        if self.progressive:
+            torch.cuda.current_stream(self.device).synchronize()
+        else:
+            torch.cuda.synchronize()
 
 
 class VC(object):
@@ -396,6 +464,253 @@ class VC(object):
         bounds.append((t if t is not None else 0, audio_pad.shape[0]))
         return bounds
 
+    # ---- whole track: the schedule's steps -------------------------------------------------------------------------------
+    def _seeded_noise(self, net_g, seed):
+        inter, upp = net_g.inter_channels, net_g.upp
+
+        def noise_fn(ci, s, e, _seed=int(seed)):
+            g = torch.Generator(device=self.device).manual_seed(_seed + ci)
+            T = 2 * ((e - s - 400) // 320 + 1)
+            return (torch.randn((1, inter, T), generator=g, device=self.device),
+                    torch.randn(T * upp, generator=g, device=self.device))
+        return noise_fn
+
+    def _load_index(self, file_index, index_rate):
+        if file_index == "" or not os.path.exists(file_index) or index_rate == 0:
+            return None, None
+        try:
+            if _env.dev("AICG_GPU_KNN", "1") != "0":
+                from . import retrieval
+                return retrieval.load_index(file_index, self.device), None   # vectors in HBM, search + mix on the device
+            import faiss   # the reference's host path: faiss search per chunk
+            index = faiss.read_index(file_index)
+            return index, index.reconstruct_n(0, index.ntotal)
+        except Exception:
+            traceback.print_exc()
+            return None, None
+
+    @staticmethod
+    def _read_f0_file(f0_file):
+        try:
+            with open(f0_file.name, "r") as f:
+                lines = f.read().strip("\n").split("\n")
+            return np.array([[float(i) for i in line.split(",")] for line in lines], dtype="float32")
+        except Exception:
+            traceback.print_exc()
+
+    def _schedule(self, net_g, if_f0, f0_method, world, inp_f0):
+        """-> (schedule, f0 segments, two_streams): which of _f0_serial / _f0_one_launch / _f0_progressive starts this call -- decided here only.
+        The f0 estimate does not depend on the HuBERT features and RMVPE's recurrent part occupies a handful of CUs, so on the GPU its
+        kernels are queued on a side stream first and the feature extraction of every chunk runs on the main stream on top of them; the
+        synthesizer passes start once both are done.  Everything is enqueued from this thread (a helper thread fights the launch loop
+        for the GIL).  AICG_OVERLAP_F0=0 restores the reference's serial order (f0, then per chunk: features, synthesis).
+        (AICG_F0_SEGMENTS on the host: the CPU tests walk the same progressive schedule, with the streams and events as no-ops;
+        "1" = the recurrence as one launch.)  One rank on a GPU takes the progressive schedule too since the f0 chain became the longer
+        branch of the phase (r4: HuBERT 74.9 ms, f0 79.4): the chunk loop then starts when HuBERT is done, on the middle chunks, while
+        the recurrence finishes the track's ends -- 718.7 -> 713.9 ms per 240 s track at 8 segments (4: 715.5, 16: 715.6)."""
+        on_gpu = self._sync()
+        env_seg = int(_env.dev("AICG_F0_SEGMENTS", "0"))
+        nseg = env_seg or (16 if world > 1 else (8 if on_gpu else 0))
+        if not (if_f0 == 1 and f0_method == "rmvpe" and (on_gpu or nseg > 1) and _env.dev("AICG_OVERLAP_F0", "1") != "0"):
+            return "serial", nseg, False
+        # Two streams: the encoder half of chunk i + 1 (text encoder + flow: ~140 short launches that leave most CUs idle and take the host
+        # about as long to queue -- 40 us each -- as the GPU to run) is queued on a second stream underneath the vocoder of chunk i
+        # (_chunk).  What that buys is small -- 2 ms per 240 s track: short launches running beside the vocoder cost it nearly what they
+        # take alone (one stream: 674.7 ms, two: 667) -- and a stream priority changes nothing.  AICG_OVERLAP_SYNTH=0: one stream.
+        two_streams = on_gpu and hasattr(net_g, "infer_front") and _env.dev("AICG_OVERLAP_SYNTH", "1") != "0"
+        # an f0 curve file (inp_f0) keeps the one-launch schedule, whose get_f0 splices it
+        return ("progressive" if nseg > 1 and inp_f0 is None else "one_launch"), nseg, two_streams
+
+    def _run_f0(self, c, raw=None):
+        pc, pcf = self.get_f0(*c.f0_args, _raw_f0=raw)
+        return (torch.tensor(pc[:c.p_len], device=self.device).unsqueeze(0).long(),
+                torch.tensor(pcf[:c.p_len], device=self.device).unsqueeze(0).float())
+
+    def _features(self, c):
+        many = self._vc_features_many(c.model, [c.pad_dev[c.bounds[ci][0]:c.bounds[ci][1]] for ci in c.mine], c.index, c.big_npy,
+                                      c.index_rate, c.version, c.protect < 0.5 and c.if_f0 == 1)
+        c.feats_of = dict(zip(c.mine, many))
+
+    def _f0_serial(self, c):
+        """The reference's order: f0 of the whole track; features and synthesis then go chunk by chunk through vc()."""
+        if c.if_f0 == 1:
+            c.pitch, c.pitchf = self._run_f0(c)
+        if self._sync():
+            torch.cuda.synchronize()
+        c.t2 = ttime()
+        c.times[1] += c.t2 - c.t1
+
+    def _open_side(self, c):
+        c.main = torch.cuda.current_stream(self.device) if c.on_gpu else _HostStream()
+        # one side stream per VC object: the caching allocator keeps a block pool per stream, a fresh stream per call
+        # would strand RMVPE's working set (a few GB for a 4-minute track) in up to 32 pools
+        c.side = getattr(self, "_f0_stream", None) if c.on_gpu else _HostStream()
+        if c.side is None:
+            # high priority: the f0 branch is a short U-Net followed by a 70 ms recurrence on four CUs; dispatched first it
+            # leaves the chip to HuBERT while the GRU runs, dispatched behind HuBERT's launches it finishes 40 ms later
+            # (AICG_F0_PRIORITY=0: default priority)
+            prio = -1 if _env.dev("AICG_F0_PRIORITY", "1") != "0" else 0
+            c.side = self._f0_stream = torch.cuda.Stream(device=self.device, priority=prio)
+        # one upload of the padded track: a pageable host->device copy on the default stream waits for the whole device,
+        # side stream included, so the chunk loop must not issue any
+        c.pad_dev = c.audio_pad.float()
+
+    def _f0_one_launch(self, c):
+        """f0 on the side stream with the recurrence as one launch, every chunk's features on `main` on top of it; the host joins both."""
+        self._open_side(c)
+        c.side.wait_stream(c.main)
+        c.tf0 = ttime()
+        with (torch.cuda.stream(c.side) if c.on_gpu else c.side):      # RMVPE is queued before HuBERT
+            f0_dev = self._rmvpe().infer_from_audio_device(c.pad_dev, thred=0.03, group=self._rmvpe_group())
+        self._features(c)
+        self._settle(c, f0_dev)
+        self._open_enc(c)
+
+    def _f0_progressive(self, c):
+        """Progressive f0 (multi-GPU: every rank runs the whole-track BiGRU, N x 32 ms for N x 240 s): the recurrence is queued in
+        segments, and the pitch of a frame range exists as soon as BOTH directions have passed it -- the middle of the track at half
+        the recurrence time, its ends last.  The chunk loop then takes this rank's chunks middle-out and waits per chunk (events), not
+        for the whole track.  Same values as the one-launch form (GruSegments); the host never sees f0.
+        NOTE: this schedule never calls get_f0 (an override of VC.get_f0 is bypassed; the estimate passes _estimated_f0 and the shared
+        _f0_tail instead)."""
+        self._open_side(c)
+        # the device-resident pitch tracks are created and filled on `main` BEFORE the side stream forks from it -- on_f0 writes
+        # slices of them on `side`, and a fill that could run after such a write would erase it (ADVICE r4)
+        c.pitch = torch.ones((1, c.p_len), dtype=torch.long, device=self.device)
+        c.pitchf = torch.zeros((1, c.p_len), dtype=torch.float32, device=self.device)
+        c.side.wait_stream(c.main)
+        c.tf0 = ttime()
+        factor = pow(2, c.f0_args[3] / 12)      # f0_up_key
+
+        def on_f0(lo, hi, f0):
+            c.publish(lo, hi, *self._f0_tail(self._estimated_f0(lo, hi, f0), factor))
+        with (torch.cuda.stream(c.side) if c.on_gpu else c.side):      # RMVPE is queued before HuBERT
+            self._rmvpe().infer_progressive(c.pad_dev, 0.03, c.nseg, on_f0, group=self._rmvpe_group())
+        c.gru_seg = self._rmvpe().last_segments
+        self._features(c)
+        # the host first queues the first chunk's encoder half and settles THEN -- its ~140 short launches take the host 6 ms to issue,
+        # which now pass under the tail of HuBERT instead of in front of the first vocoder
+        self._open_enc(c)
+        self._settle(c)
+
+    def _settle(self, c, f0_dev=None):
+        """The host meets the device: every chunk's features exist.  Under the one-launch schedule (`f0_dev`: the estimate queued on the
+        side stream) it waits for f0 as well and turns it into the pitch tracks; the progressive schedule's pitch arrives during the
+        chunk loop.  times[1] is the f0 branch's own wall time (it overlaps times[0])."""
+        c.main.synchronize()
+        tf1 = c.t2 = ttime()
+        # an early exchange timeout: do not synthesise a whole track from invalid pitch
+        c.f0_bad = bool(c.progressive and c.gru_seg.timed_out())
+        if f0_dev is not None:
+            c.side.synchronize()
+            c.main.wait_stream(c.side)
+            f0_host = f0_dev.cpu().numpy()
+            if ops.gru_timed_out():  # multi-workgroup GRU starved of its partners under the HuBERT load: single-workgroup rerun
+                f0_host = self._rmvpe().infer_from_audio_device(c.pad_dev, thred=0.03, two_workgroups=False).cpu().numpy()
+            c.pitch, c.pitchf = self._run_f0(c, f0_host)
+            c.t2 = ttime()
+        c.f0_wait = c.t2 - tf1
+        c.times[0] += tf1 - c.tf0
+        c.times[1] += c.t2 - c.tf0
+
+    def _open_enc(self, c):
+        """Two streams: fork the encoder-half stream from `main` and queue the first chunk's encoder half on it."""
+        if not c.two_streams:
+            return
+        c.enc = getattr(self, "_enc_stream", None)
+        if c.enc is None:
+            c.enc = self._enc_stream = torch.cuda.Stream(device=self.device)
+        c.enc.wait_stream(c.main)          # features, pitch tracks, sid: everything the fronts read exists on `main` by now
+        if c.order():
+            self._queue_front(c, c.order()[0])
+
+    def _queue_front(self, c, ci):
+        s, e = c.bounds[ci]
+        pc, pcf = c.chunk_pitch(ci)
+        feats, feats0 = c.feats_of.pop(ci)
+        c.wait_pitch(c.enc, ci)
+        with torch.cuda.stream(c.enc):
+            noise = c.noise(ci)
+            st = self._vc_synth_front(c.net_g, c.sid, e - s, feats, feats0, pc, pcf, c.protect, noise)
+            ev = torch.cuda.Event()
+            ev.record(c.enc)
+        c.fronts[ci] = (st, ev, (feats, feats0, pc, pcf, noise))
+
+    def _chunk(self, c, ci, front=None, after=None):
+        """Synthesise chunk `ci` and keep its trimmed piece -- the one place a chunk becomes audio, whatever the schedule and in recovery.
+        `front`: its encoder half as _queue_front left it (two streams).  Then the HOST queues the vocoder of chunk i first and the
+        encoder half of chunk i + 1 behind it: the other way round the main stream stood idle for the 6 ms the host needs to issue the
+        short launches (kernel trace of round 5, profiles/r05_timeline.json: 6.5 + 6.1 ms at two chunk boundaries, the first vocoder
+        behind TWO encoder halves)."""
+        s, e = c.bounds[ci]
+        pc, pcf = c.chunk_pitch(ci)
+        if not c.overlap:       # serial: vc() runs features and synthesis and accumulates times[0] / times[2] itself
+            out = self.vc(c.model, c.net_g, c.sid, c.audio_pad[s:e], pc, pcf, c.times, c.index, c.big_npy, c.index_rate, c.version,
+                          c.protect, noise=c.noise(ci), keep_on_device=True)
+        else:
+            noise = c.noise(ci) if front is None else None
+            ts0 = ttime()
+            if front is not None:
+                st, ev, keep = front    # the front's inputs stay referenced until the drain below: nothing is recycled under the other stream
+                c.main.wait_event(ev)
+                out = self._vc_synth_back(c.net_g, st)[0, 0]
+                if after is not None:
+                    self._queue_front(c, after)
+            else:
+                feats, feats0 = c.feats_of.pop(ci)
+                c.wait_pitch(c.main, ci)
+                out = self._vc_synth(c.net_g, c.sid, e - s, feats, feats0, pc, pcf, c.protect, noise)[0, 0]
+            c.drain()
+            c.times[2] += ttime() - ts0
+        c.pieces[ci] = out[self.t_pad_tgt: -self.t_pad_tgt]
+        return c.pieces[ci]
+
+    def _chunk_loop(self, c):
+        order = c.order()
+        for ci, after in zip(order, order[1:] + [None]):
+            if c.f0_bad:
+                break
+            self._chunk(c, ci, c.fronts.pop(ci, None), after)
+            if c.progressive and c.gru_seg.timed_out():    # polled per chunk (4 bytes): at most one chunk is synthesised from bad pitch
+                c.f0_bad = True
+        if c.progressive:
+            if c.on_gpu:
+                torch.cuda.synchronize()
+            c.fronts.clear()
+
+    def _recover(self, c):
+        """The multi-workgroup recurrence starved of its partners (a busy or shared GPU): this rank's f0 is invalid.  Recompute it locally
+        on the single-workgroup kernel (no collective: the other ranks may be fine) and redo this rank's chunks."""
+        warnings.warn("aicovergen_amd: the multi-workgroup BiGRU timed out waiting for its partner workgroups (busy or shared GPU); "
+                      "f0 and this rank's chunks are recomputed on the single-workgroup kernel -- this call costs about twice "
+                      "its usual time", RuntimeWarning)
+        c.pitch, c.pitchf = self._run_f0(c, self._rmvpe().infer_from_audio_device(c.pad_dev, thred=0.03, two_workgroups=False).cpu().numpy())
+        self._features(c)
+        for ci in c.mine:
+            self._chunk(c, ci)
+        if c.on_gpu:
+            torch.cuda.synchronize()
+
+    def _post(self, audio_opt, audio, tgt_sr, resample_sr, rms_mix_rate):
+        """The joined float32 track at tgt_sr -> the call's int16 result: RMS mix with the input, peak limit, truncating cast (reference :639-651)."""
+        if resample_sr >= 16000 and tgt_sr != resample_sr:
+            # optional output resampling (rvc_infer passes resample_sr=0): host fallback, not on the hot path
+            a = audio_opt.cpu().numpy()
+            if rms_mix_rate != 1:
+                a = change_rms(audio.cpu().numpy(), 16000, a, tgt_sr, rms_mix_rate)
+            g = np.gcd(int(tgt_sr), int(resample_sr))
+            audio_opt = torch.from_numpy(signal.resample_poly(a, resample_sr // g, tgt_sr // g).astype(np.float32)).to(self.device)
+        elif rms_mix_rate != 1:
+            # change_rms on the device: frame RMS envelopes (1 s frames, 0.5 s hop), linear interpolation, power mix
+            rms1 = ops.frame_rms(audio, 16000 // 2 * 2, 16000 // 2)
+            rms2 = ops.frame_rms(audio_opt, tgt_sr // 2 * 2, tgt_sr // 2)
+            ops.rms_mix_(audio_opt, rms1, rms2, rms_mix_rate)
+        audio_max = float(ops.absmax(audio_opt).item()) / 0.99
+        max_int16 = 32768
+        if audio_max > 1:
+            max_int16 /= audio_max
+        return ops.to_int16(audio_opt, max_int16).cpu().numpy()
+
     @_bracket_pipeline
     def pipeline(self, model, net_g, sid, audio, input_audio_path, times, f0_up_key, f0_method, file_index, index_rate,
                  if_f0, filter_radius, tgt_sr, resample_sr, rms_mix_rate, version, protect, crepe_hop_length, f0_file=None,
@@ -408,304 +723,36 @@ class VC(object):
         rank owns; outputs of different world sizes agree to ~1e-6 relative (tests/test_dist.py states the bound), ranks of one run
         agree bit for bit; `group` shards the chunk loop over the ranks of a torch.distributed process group."""
         if noise_fn is None and noise_seed is not None:
-            inter, upp = net_g.inter_channels, net_g.upp
-
-            def noise_fn(ci, s, e, _seed=int(noise_seed)):
-                g = torch.Generator(device=self.device).manual_seed(_seed + ci)
-                T = 2 * ((e - s - 400) // 320 + 1)
-                return (torch.randn((1, inter, T), generator=g, device=self.device),
-                        torch.randn(T * upp, generator=g, device=self.device))
-        index = big_npy = None
-        if file_index != "" and os.path.exists(file_index) and index_rate != 0:
-            try:
-                if _env.dev("AICG_GPU_KNN", "1") != "0":
-                    from . import retrieval
-                    index = retrieval.load_index(file_index, self.device)   # vectors in HBM, search + mix on the device
-                else:
-                    import faiss   # the reference's host path: faiss search per chunk
-                    index = faiss.read_index(file_index)
-                    big_npy = index.reconstruct_n(0, index.ntotal)
-            except Exception:
-                traceback.print_exc()
-                index = big_npy = None
+            noise_fn = self._seeded_noise(net_g, noise_seed)
+        index, big_npy = self._load_index(file_index, index_rate)
         self._group = group   # the crepe f0 methods shard their frames over it, RMVPE its U-Net
         tp0 = ttime()
         audio, audio_pad, opt_ts, p_len = self.plan(audio)
         t1 = ttime()
-        inp_f0 = None
-        if hasattr(f0_file, "name"):
-            try:
-                with open(f0_file.name, "r") as f:
-                    lines = f.read().strip("\n").split("\n")
-                inp_f0 = np.array([[float(i) for i in line.split(",")] for line in lines], dtype="float32")
-            except Exception:
-                traceback.print_exc()
+        inp_f0 = self._read_f0_file(f0_file) if hasattr(f0_file, "name") else None
         sid = torch.tensor(sid, device=self.device).unsqueeze(0).long()
         bounds = self.chunk_bounds(audio_pad, opt_ts)
         rank, world = adist.world(group)
-        mine = [ci for ci in range(len(bounds)) if ci % world == rank]
-        pitch, pitchf = None, None
-        use_protect = protect < 0.5 and if_f0 == 1
-
-        def run_f0(raw=None):
-            pc, pcf = self.get_f0(input_audio_path, audio_pad, p_len, f0_up_key, f0_method, filter_radius,
-                                  crepe_hop_length, inp_f0, _raw_f0=raw)
-            return (torch.tensor(pc[:p_len], device=self.device).unsqueeze(0).long(),
-                    torch.tensor(pcf[:p_len], device=self.device).unsqueeze(0).float())
-
-        # The f0 estimate does not depend on the HuBERT features and RMVPE's recurrent part occupies a handful of CUs, so on
-        # the GPU its kernels are queued on a side stream first and the feature extraction of every chunk runs on the main
-        # stream on top of them; the synthesizer passes start once both are done.  Everything is enqueued from this thread
-        # (a helper thread fights the launch loop for the GIL).  AICG_OVERLAP_F0=0 restores the reference's serial order
-        # (f0, then per chunk: features, synthesis).
-        on_gpu = self._sync()
-        # (AICG_F0_SEGMENTS on the host: the CPU tests walk the same progressive schedule, with the streams and events as no-ops;
-        #  "1" = the recurrence as one launch.)  One rank on a GPU takes the progressive schedule too since the f0 chain became the
-        #  longer branch of the phase (r4: HuBERT 74.9 ms, f0 79.4): the chunk loop then starts when HuBERT is done, on the middle chunks,
-        #  while the recurrence finishes the track's ends -- 718.7 -> 713.9 ms per 240 s track at 8 segments (4: 715.5, 16: 715.6).
-        env_seg = int(_env.dev("AICG_F0_SEGMENTS", "0"))
-        nseg = env_seg or (16 if world > 1 else (8 if on_gpu else 0))
-        overlap = (if_f0 == 1 and f0_method == "rmvpe" and (on_gpu or nseg > 1)
-                   and _env.dev("AICG_OVERLAP_F0", "1") != "0")
-        feats_of = {}
-        f0_wait = 0.0
-        gru_seg = None        # progressive f0: the recurrence's handle (its exchange-timeout word is polled between chunks)
-        f0_bad = False
-        marks = []            # progressive f0: (first frame, end frame, event) -- the frame range whose pitch exists once the event has fired
-        progressive = False
-        if overlap:
-            main = torch.cuda.current_stream(self.device) if on_gpu else _HostStream()
-            # one side stream per VC object: the caching allocator keeps a block pool per stream, a fresh stream per call
-            # would strand RMVPE's working set (a few GB for a 4-minute track) in up to 32 pools
-            side = getattr(self, "_f0_stream", None) if on_gpu else _HostStream()
-            if side is None:
-                # high priority: the f0 branch is a short U-Net followed by a 70 ms recurrence on four CUs; dispatched first it
-                # leaves the chip to HuBERT while the GRU runs, dispatched behind HuBERT's launches it finishes 40 ms later
-                # (AICG_F0_PRIORITY=0: default priority)
-                prio = -1 if _env.dev("AICG_F0_PRIORITY", "1") != "0" else 0
-                side = self._f0_stream = torch.cuda.Stream(device=self.device, priority=prio)
-            # one upload of the padded track: a pageable host->device copy on the default stream waits for the whole device,
-            # side stream included, so the chunk loop below must not issue any
-            pad_dev = audio_pad.float()
-            # Progressive f0 (see below): the device-resident pitch tracks are created and filled on `main` BEFORE the side stream forks
-            # from it -- on_f0 writes slices of them on `side`, and a fill that could run after such a write would erase it (ADVICE r4)
-            progressive = nseg > 1 and inp_f0 is None
-            if progressive:
-                pitch = torch.ones((1, p_len), dtype=torch.long, device=self.device)
-                pitchf = torch.zeros((1, p_len), dtype=torch.float32, device=self.device)
-            side.wait_stream(main)
-            tf0 = ttime()
-            # Progressive f0 (multi-GPU: every rank runs the whole-track BiGRU, N x 32 ms for N x 240 s): the recurrence is queued in
-            # segments, and the pitch of a frame range exists as soon as BOTH directions have passed it -- the middle of the track at
-            # half the recurrence time, its ends last.  The chunk loop below then takes this rank's chunks middle-out and waits per
-            # chunk (events), not for the whole track.  Same values as the one-launch form (GruSegments); the host never sees f0.
-            # NOTE: this schedule never calls get_f0 (an override of VC.get_f0 is bypassed; the estimate passes _estimated_f0 and the
-            # shared _f0_tail instead); an f0 curve file (inp_f0) keeps the one-launch schedule, whose get_f0 splices it.
-            if progressive:
-                cover = [p_len, 0]
-
-                def on_f0(lo, hi, f0, _factor=pow(2, f0_up_key / 12)):
-                    f0bak, coarse = self._f0_tail(self._estimated_f0(lo, hi, f0), _factor)
-                    hi2 = min(hi, p_len)
-                    if lo < hi2:
-                        pitch[0, lo:hi2] = coarse[: hi2 - lo]
-                        pitchf[0, lo:hi2] = f0bak[: hi2 - lo].float()
-                    cover[0], cover[1] = min(cover[0], lo), max(cover[1], hi2)
-                    ev = torch.cuda.Event() if on_gpu else _HostEvent()
-                    ev.record(side)
-                    marks.append((cover[0], cover[1], ev))
-
-                with (torch.cuda.stream(side) if on_gpu else side):
-                    self._rmvpe().infer_progressive(pad_dev, 0.03, nseg, on_f0, group=self._rmvpe_group())
-                gru_seg = self._rmvpe().last_segments
-            else:
-                with (torch.cuda.stream(side) if on_gpu else side):
-                    f0_dev = self._rmvpe().infer_from_audio_device(pad_dev, thred=0.03, group=self._rmvpe_group())
-            many = self._vc_features_many(model, [pad_dev[bounds[ci][0]:bounds[ci][1]] for ci in mine], index, big_npy, index_rate,
-                                          version, use_protect)
-            feats_of = dict(zip(mine, many))
-
-            def settle():
-                """The host meets the device: every chunk's features exist.  -> (time, f0 already known to be invalid)"""
-                main.synchronize()
-                # an early exchange timeout: do not synthesise a whole track from invalid pitch
-                return ttime(), bool(progressive and gru_seg.timed_out())
-
-            # Progressive: the host first queues the first chunk's encoder half (below) and settles THEN -- its ~140 short launches
-            # take the host 6 ms to issue, which now pass under the tail of HuBERT instead of in front of the first vocoder.
-            settle_later = progressive
-            if not settle_later:
-                tf1, f0_bad = settle()
-            if not progressive:
-                side.synchronize()
-                main.wait_stream(side)
-                f0_host = f0_dev.cpu().numpy()
-                if ops.gru_timed_out():  # multi-workgroup GRU starved of its partners under the HuBERT load: single-workgroup rerun
-                    f0_host = self._rmvpe().infer_from_audio_device(pad_dev, thred=0.03, two_workgroups=False).cpu().numpy()
-                pitch, pitchf = run_f0(f0_host)
-                del f0_dev
-            if not settle_later:
-                t2 = ttime()
-                f0_wait = t2 - tf1
-                times[0] += tf1 - tf0
-                times[1] += t2 - tf0  # the f0 branch's own wall time (it overlaps times[0])
-        else:
-            settle_later = False
-            if if_f0 == 1:
-                pitch, pitchf = run_f0()
-            if self._sync():
-                torch.cuda.synchronize()
-            t2 = ttime()
-            times[1] += t2 - t1
-        pieces = {}
-
-        def frames_of(ci):
-            s, e = bounds[ci]
-            return s // self.window, (p_len if ci == len(bounds) - 1 else (e - self.window) // self.window)
-
-        def mark_of(ci):      # index of the first mark whose range covers the chunk's frames
-            fa, fb = frames_of(ci)
-            for m, (lo, hi, _) in enumerate(marks):
-                if lo <= fa and min(fb, p_len) <= hi:
-                    return m
-            return len(marks) - 1
-
-        order = sorted(mine, key=lambda ci: (mark_of(ci), ci)) if progressive else list(mine)
-
-        def chunk_pitch(ci):
-            s, e = bounds[ci]
-            if if_f0 != 1:
-                return None, None
-            pe = None if ci == len(bounds) - 1 else (e - self.window) // self.window
-            return pitch[:, s // self.window: pe], pitchf[:, s // self.window: pe]
-
-        # Overlapped schedule: the encoder half of chunk i + 1 (text encoder + flow: ~140 short launches that leave most CUs idle
-        # and take the host about as long to queue -- 40 us each -- as the GPU to run) is queued on a second stream underneath the
-        # vocoder of chunk i.  The HOST queues the vocoder of chunk i first and the encoder half of chunk i + 1 behind it: the other way
-        # round the main stream stood idle for the 6 ms the host needs to issue the short launches (kernel trace of round 5,
-        # profiles/r05_timeline.json: 6.5 + 6.1 ms at two chunk boundaries, the first vocoder behind TWO encoder halves).  What that
-        # buys is small -- 2 ms per 240 s track: short launches running beside the vocoder cost it nearly what they take alone
-        # (one stream: 674.7 ms, two: 667) -- and a stream priority changes nothing.  AICG_OVERLAP_SYNTH=0: one stream.
-        two_streams = overlap and on_gpu and hasattr(net_g, "infer_front") and _env.dev("AICG_OVERLAP_SYNTH", "1") != "0"
-        fronts = {}
-        if two_streams:
-            main = torch.cuda.current_stream(self.device)
-            enc = getattr(self, "_enc_stream", None)
-            if enc is None:
-                enc = self._enc_stream = torch.cuda.Stream(device=self.device)
-            enc.wait_stream(main)          # features, pitch tracks, sid: everything the fronts read exists on `main` by now
-
-            def queue_front(ci):
-                s, e = bounds[ci]
-                pc, pcf = chunk_pitch(ci)
-                feats, feats0 = feats_of.pop(ci)
-                if progressive:
-                    enc.wait_event(marks[mark_of(ci)][2])      # this chunk's pitch frames exist
-                with torch.cuda.stream(enc):
-                    noise = noise_fn(ci, s, e) if noise_fn is not None else None
-                    st = self._vc_synth_front(net_g, sid, e - s, feats, feats0, pc, pcf, protect, noise)
-                    ev = torch.cuda.Event()
-                    ev.record(enc)
-                # the inputs stay referenced until the chunk's synchronize below: nothing is recycled under the other stream
-                fronts[ci] = (st, ev, (feats, feats0, pc, pcf, noise))
-
-            if order:
-                queue_front(order[0])
-        if settle_later:
-            tf1, f0_bad = settle()
-            t2 = tf1
-            times[0] += tf1 - tf0
-            times[1] += t2 - tf0
-
-        def drain():          # the chunk's work is done (progressive: without waiting for the f0 stream's remaining segments)
-            if not on_gpu:
-                return
-            if progressive:
-                torch.cuda.current_stream(self.device).synchronize()
-            else:
-                torch.cuda.synchronize()
-
-        for k, ci in enumerate(order):
-            if f0_bad:
-                break
-            s, e = bounds[ci]
-            pc, pcf = chunk_pitch(ci)
-            if two_streams:
-                ts0 = ttime()
-                st, ev, keep = fronts.pop(ci)
-                main.wait_event(ev)
-                out = self._vc_synth_back(net_g, st)[0, 0]
-                if k + 1 < len(order):
-                    queue_front(order[k + 1])
-                drain()
-                del st, keep
-                times[2] += ttime() - ts0
-            elif overlap:
-                noise = noise_fn(ci, s, e) if noise_fn is not None else None
-                ts0 = ttime()
-                feats, feats0 = feats_of.pop(ci)
-                if progressive and on_gpu:
-                    torch.cuda.current_stream(self.device).wait_event(marks[mark_of(ci)][2])
-                out = self._vc_synth(net_g, sid, e - s, feats, feats0, pc, pcf, protect, noise)[0, 0]
-                drain()
-                times[2] += ttime() - ts0
-            else:
-                noise = noise_fn(ci, s, e) if noise_fn is not None else None
-                out = self.vc(model, net_g, sid, audio_pad[s:e], pc, pcf, times, index, big_npy, index_rate, version, protect,
-                              noise=noise, keep_on_device=True)
-            pieces[ci] = out[self.t_pad_tgt: -self.t_pad_tgt]
-            if progressive and gru_seg.timed_out():    # polled per chunk (4 bytes): at most one chunk is synthesised from bad pitch
-                f0_bad = True
-        if progressive:
-            if on_gpu:
-                torch.cuda.synchronize()
-            fronts.clear()
-            if ops.gru_timed_out() or f0_bad:
-                # the multi-workgroup recurrence starved of its partners (a busy or shared GPU): this rank's f0 is invalid.  Recompute
-                # it locally on the single-workgroup kernel (no collective: the other ranks may be fine) and redo this rank's chunks
-                import warnings
-                warnings.warn("aicovergen_amd: the multi-workgroup BiGRU timed out waiting for its partner workgroups (busy or shared GPU); "
-                              "f0 and this rank's chunks are recomputed on the single-workgroup kernel -- this call costs about twice "
-                              "its usual time", RuntimeWarning)
-                f0_host = self._rmvpe().infer_from_audio_device(audio_pad.float(), thred=0.03, two_workgroups=False).cpu().numpy()
-                pitch, pitchf = run_f0(f0_host)
-                many = self._vc_features_many(model, [audio_pad.float()[bounds[ci][0]:bounds[ci][1]] for ci in mine], index, big_npy,
-                                              index_rate, version, use_protect)
-                for ci, (feats, feats0) in zip(mine, many):
-                    s, e = bounds[ci]
-                    pc, pcf = chunk_pitch(ci)
-                    noise = noise_fn(ci, s, e) if noise_fn is not None else None
-                    out = self._vc_synth(net_g, sid, e - s, feats, feats0, pc, pcf, protect, noise)[0, 0]
-                    pieces[ci] = out[self.t_pad_tgt: -self.t_pad_tgt]
-                if on_gpu:
-                    torch.cuda.synchronize()
+        schedule, nseg, two_streams = self._schedule(net_g, if_f0, f0_method, world, inp_f0)
+        c = _Call(device=self.device, on_gpu=self._sync(), window=self.window, model=model, net_g=net_g, sid=sid, index=index,
+                  big_npy=big_npy, index_rate=index_rate, version=version, protect=protect, if_f0=if_f0, noise_fn=noise_fn, times=times,
+                  f0_args=(input_audio_path, audio_pad, p_len, f0_up_key, f0_method, filter_radius, crepe_hop_length, inp_f0),
+                  audio_pad=audio_pad, bounds=bounds, mine=[ci for ci in range(len(bounds)) if ci % world == rank], p_len=p_len,
+                  schedule=schedule, nseg=nseg, two_streams=two_streams, t1=t1)
+        # f0 and features: queued (overlapped schedules) or done (serial) when this returns; c.t2 is set
+        {"serial": self._f0_serial, "one_launch": self._f0_one_launch, "progressive": self._f0_progressive}[schedule](c)
+        self._chunk_loop(c)
+        if c.progressive and (ops.gru_timed_out() or c.f0_bad):
+            self._recover(c)
         tc1 = ttime()
-        pieces = adist.gather_pieces(pieces, len(bounds), self.device, group)
+        pieces = adist.gather_pieces(c.pieces, len(bounds), self.device, group)
         tj1 = ttime()
-        audio_opt = torch.cat([pieces[i] for i in range(len(bounds))]).contiguous()
-        if resample_sr >= 16000 and tgt_sr != resample_sr:
-            # optional output resampling (rvc_infer passes resample_sr=0): host fallback, not on the hot path
-            a = audio_opt.cpu().numpy()
-            if rms_mix_rate != 1:
-                a = change_rms(audio.cpu().numpy(), 16000, a, tgt_sr, rms_mix_rate)
-            from scipy.signal import resample_poly
-            g = np.gcd(int(tgt_sr), int(resample_sr))
-            audio_opt = torch.from_numpy(resample_poly(a, resample_sr // g, tgt_sr // g).astype(np.float32)).to(self.device)
-        elif rms_mix_rate != 1:
-            # change_rms on the device: frame RMS envelopes (1 s frames, 0.5 s hop), linear interpolation, power mix
-            rms1 = ops.frame_rms(audio, 16000 // 2 * 2, 16000 // 2)
-            rms2 = ops.frame_rms(audio_opt, tgt_sr // 2 * 2, tgt_sr // 2)
-            ops.rms_mix_(audio_opt, rms1, rms2, rms_mix_rate)
-        audio_max = float(ops.absmax(audio_opt).item()) / 0.99
-        max_int16 = 32768
-        if audio_max > 1:
-            max_int16 /= audio_max
-        audio_opt = ops.to_int16(audio_opt, max_int16).cpu().numpy()
+        audio_opt = self._post(torch.cat([pieces[i] for i in range(len(bounds))]).contiguous(), audio, tgt_sr, resample_sr, rms_mix_rate)
         # wall-clock split of this call (host pre-processing, f0, chunk loop, join + host post-processing)
         # (overlapped schedule: f0_s = features of every chunk with the f0 branch underneath, f0_wait_s of it spent waiting for f0)
-        self.last_profile = {"plan_s": t1 - tp0, "f0_s": t2 - t1, "chunks_s": tc1 - t2, "post_s": ttime() - tc1,
-                             "f0_wait_s": f0_wait, "overlap_f0": float(bool(overlap)), "join_s": tj1 - tc1,
-                             "f0_progressive": float(bool(progressive))}
+        self.last_profile = {"plan_s": t1 - tp0, "f0_s": c.t2 - t1, "chunks_s": tc1 - c.t2, "post_s": ttime() - tc1,
+                             "f0_wait_s": c.f0_wait, "overlap_f0": float(c.overlap), "join_s": tj1 - tc1,
+                             "f0_progressive": float(c.progressive)}
         return audio_opt
 
 

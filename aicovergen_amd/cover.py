@@ -10,6 +10,9 @@ File level, with main.py's signatures and output names:
     combine_audio(audio_paths, output_path, main_gain, backup_gain, inst_gain, output_format)
     pitch_shift(audio_path, pitch_change) -> '<stem>_p{pitch_change}.wav'   (main.py:138-147, `-pall N`)
 and on a signal: pitch_shift_signal(x, sr, semitones, offsets=None) -> (y, offsets): sox's `pitch` as WSOLA + resampling (csrc/pitch.hip)
+The whole cover in one call, stems handed from stage to stage in device memory:
+    CoverSession(mdxnet_models_dir, rvc_models_dir, output_dir).song_cover_pipeline(song_input, voice_model, pitch_change, keep_files, ...)
+    song_cover_pipeline(...) with a default session, and `python -m aicovergen_amd.cover` with main.py's flags (src/main.py:236-339)
 
 Parameters become coefficients here, in float32 the way JUCE derives them; the recurrences and the mix run in
 csrc/fx.hip.  The effects are computed in segments that restart from zero state `warm` samples early; the warm-up is chosen so that
@@ -332,3 +335,335 @@ def combine_audio(audio_paths, output_path, main_gain, backup_gain, inst_gain, o
     t = [(torch.from_numpy(np.ascontiguousarray(d)).to(dev), sr) for d, sr in stems]
     out, sr = mix_stems(t[0][0], t[0][1], t[1][0], t[1][1], t[2][0], t[2][1], main_gain, backup_gain, inst_gain)
     export(out.cpu().numpy(), sr, output_path, output_format)
+
+
+# ---------------------------------------------------------------------------------------------------
+# The whole cover in one call (main.py's song_cover_pipeline, src/main.py:236-313)
+# ---------------------------------------------------------------------------------------------------
+MDX_MODEL_FILES = ("UVR-MDX-NET-Voc_FT.onnx", "UVR_MDXNET_KARA_2.onnx", "Reverb_HQ_By_FoxJoy.onnx")     # main.py:182,185,188
+BASE_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+VOICE_CACHE = 4     # voice models a session keeps (the least recently used one leaves)
+
+
+def get_hash(filepath):
+    """main.py:150-156: the song id of a local file."""
+    import hashlib
+    h = hashlib.blake2b()
+    with open(filepath, "rb") as f:
+        for chunk in iter(lambda: f.read(8192), b""):
+            h.update(chunk)
+    return h.hexdigest()[:11]
+
+
+def get_audio_paths(song_dir):
+    """main.py:105-122: (original song, instrumental, de-reverbed main vocals, backup vocals) found again by suffix, None if absent."""
+    orig = inst = dereverb = backup = None
+    for file in os.listdir(song_dir):
+        if file.endswith("_Instrumental.wav"):
+            inst = os.path.join(song_dir, file)
+            orig = inst.replace("_Instrumental", "")
+        elif file.endswith("_Vocals_Main_DeReverb.wav"):
+            dereverb = os.path.join(song_dir, file)
+        elif file.endswith("_Vocals_Backup.wav"):
+            backup = os.path.join(song_dir, file)
+    return orig, inst, dereverb, backup
+
+
+def get_rvc_model(rvc_models_dir, voice_model):
+    """main.py:88-102: (the directory's .pth, its .index or '')."""
+    model_dir = os.path.join(rvc_models_dir, voice_model)
+    pth = index = None
+    for file in os.listdir(model_dir):
+        ext = os.path.splitext(file)[1]
+        if ext == ".pth":
+            pth = file
+        if ext == ".index":
+            index = file
+    if pth is None:
+        raise FileNotFoundError(f"No model file exists in {model_dir}.")
+    return os.path.join(model_dir, pth), os.path.join(model_dir, index) if index else ""
+
+
+class _NoStream:
+    """The host emulator runs every kernel synchronously: hand-overs between streams are already ordered."""
+
+    def wait_stream(self, other): pass
+    def __enter__(self): return self
+    def __exit__(self, *a): return False
+
+
+class _Fetch:
+    """Device tensors on their way to files.  Each copy to the host is queued on a stream of its own into pinned memory right after the
+    kernel that produced the tensor, so neither the device queue nor the host thread waits for it; the files are written when the
+    call has queued everything else."""
+
+    def __init__(self, on_gpu):
+        self.stream = torch.cuda.Stream() if on_gpu else None
+        self.jobs = []
+
+    def add(self, writer, path, t, *args):
+        if self.stream is None:
+            self.jobs.append((writer, path, t, None, args))
+            return
+        self.stream.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(self.stream):
+            host = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+            host.copy_(t, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(self.stream)
+        t.record_stream(self.stream)
+        self.jobs.append((writer, path, host, done, args))
+
+    def flush(self):
+        for writer, path, host, done, args in self.jobs:
+            if done is not None:
+                done.synchronize()
+            writer(path, host.numpy(), *args)
+        self.jobs = []
+
+
+def _write_wavfile(path, pcm, sr):      # what run_mdx (soundfile's PCM-16) and rvc_infer leave: scipy's writer on int16 samples
+    from scipy.io import wavfile
+    wavfile.write(path, int(sr), pcm)
+
+
+def _planar(pcm):
+    """(frames, C) int16 PCM -> (C, frames) float32 / 32768: what read_float makes of the stem's file."""
+    return pcm.t().contiguous().to(torch.float32) / 32768.0
+
+
+class CoverSession:
+    """The models of a cover, loaded once: the three MDX-Net sessions (model_data.json entries looked up by hash, as run_mdx does),
+    HuBERT, and a small cache of voice models by directory name.  A second song through the same session reloads nothing."""
+
+    def __init__(self, mdxnet_models_dir, rvc_models_dir, output_dir, device=None):
+        import json
+        from . import mdx, rvc
+        self.mdxnet_models_dir, self.rvc_models_dir, self.output_dir = mdxnet_models_dir, rvc_models_dir, output_dir
+        self.device = "cuda:0" if device is None else device           # main.py:195
+        with open(os.path.join(mdxnet_models_dir, "model_data.json")) as f:
+            self.mdx_model_params = json.load(f)
+        self.mdx_sessions = [mdx.load_session(self.mdx_model_params, os.path.join(mdxnet_models_dir, name)) for name in MDX_MODEL_FILES]
+        self.config = rvc.Config(self.device, True)                      # main.py:196
+        self.hubert = rvc.load_hubert(self.device, self.config.is_half, os.path.join(rvc_models_dir, "hubert_base.pt"))
+        self.voices = {}                                                 # directory name -> (cpt, version, net_g, tgt_sr, vc, index path)
+        self.profile_stages = False      # True: drain the device after every stage and keep the wall-clock split in last_profile
+        self.last_profile = {}
+
+    def voice(self, voice_model):
+        from . import rvc
+        if voice_model in self.voices:
+            self.voices[voice_model] = self.voices.pop(voice_model)      # most recently used last
+        else:
+            pth, index = get_rvc_model(self.rvc_models_dir, voice_model)
+            self.voices[voice_model] = rvc.get_vc(self.device, self.config.is_half, self.config, pth) + (index,)
+            rmvpe = os.path.join(self.rvc_models_dir, "rmvpe.pt")          # where main.py keeps it (src/vc_infer_pipeline.py:327)
+            if os.path.exists(rmvpe):
+                self.voices[voice_model][4].rmvpe_path = rmvpe
+            while len(self.voices) > VOICE_CACHE:
+                self.voices.pop(next(iter(self.voices)))
+        return self.voices[voice_model]
+
+    # ---- stages ------------------------------------------------------------------------------------------------------------
+    def _mark(self, name, t0):
+        import time
+        if self.profile_stages:
+            if _lib.backend() == "hip":
+                torch.cuda.synchronize()
+            self.last_profile[name] = self.last_profile.get(name, 0.0) + time.perf_counter() - t0
+        return time.perf_counter()
+
+    def _separate(self, song_path, song_dir, keep_files, fetch):
+        """main.py's preprocess_song (:166-190) on the device -> (instrumental, backup, de-reverbed main) int16 (frames, 2) tensors."""
+        from . import audio_io, mdx
+        dev = self.mdx_sessions[0].device
+        base = os.path.splitext(os.path.basename(song_path))[0]
+        wave, sr = audio_io.load_wav(song_path, 44100, mono=False)
+        song = torch.from_numpy(np.ascontiguousarray(wave, dtype=np.float32)).to(dev)
+        path = lambda stem: os.path.join(song_dir, "%s_%s.wav" % (base, stem))
+        vocals, inst = mdx.run_mdx_device(self.mdx_sessions[0], song, True)
+        fetch.add(_write_wavfile, path("Instrumental"), inst, sr)
+        if keep_files:
+            fetch.add(_write_wavfile, path("Vocals"), vocals, sr)
+        backup, main = mdx.run_mdx_device(self.mdx_sessions[1], vocals, True)
+        fetch.add(_write_wavfile, path("Vocals_Backup"), backup, sr)
+        if keep_files:
+            fetch.add(_write_wavfile, path("Vocals_Main"), main, sr)
+        _, dereverb = mdx.run_mdx_device(self.mdx_sessions[2], main, True, exclude_main=True)
+        fetch.add(_write_wavfile, path("Vocals_Main_DeReverb"), dereverb, sr)
+        return song_path, path("Instrumental"), path("Vocals_Main_DeReverb"), path("Vocals_Backup"), inst, backup, dereverb
+
+    def _convert(self, voice_model, dereverb, dereverb_path, pitch_change, f0_method, index_rate, filter_radius, rms_mix_rate, protect,
+                 crepe_hop_length, noise_seed):
+        """main.py's voice_change (:193-203) without the file on either side: the de-reverbed stem -> 16 kHz mono on the device
+        (ops.resample_poly_mono, bench.py's hand-over) -> VC.pipeline -> (int16 (n,) device tensor, its rate)."""
+        cpt, version, net_g, tgt_sr, vc, index_path = self.voice(voice_model)
+        audio = ops.resample_poly_mono(_planar(dereverb), 44100, 16000)
+        out = vc.pipeline(self.hubert, net_g, 0, audio, dereverb_path, [0, 0, 0], pitch_change, f0_method, index_path, index_rate,
+                          cpt.get("f0", 1), filter_radius, tgt_sr, 0, rms_mix_rate, version, protect, crepe_hop_length,
+                          noise_seed=noise_seed, device_out=True)
+        return out, tgt_sr
+
+    def song_cover_pipeline(self, song_input, voice_model, pitch_change, keep_files, is_webui=0, main_gain=0, backup_gain=0,
+                            inst_gain=0, index_rate=0.5, filter_radius=3, rms_mix_rate=0.25, f0_method='rmvpe', crepe_hop_length=128,
+                            protect=0.33, pitch_change_all=0, reverb_rm_size=0.15, reverb_wet=0.2, reverb_dry=0.8,
+                            reverb_damping=0.7, output_format='mp3', progress=None, noise_seed=None):
+        """main.py's song_cover_pipeline (src/main.py:236-313) with its parameters, defaults, file names and return value (the
+        cover's path); `is_webui` and `progress` are accepted and ignored, `noise_seed` seeds the synthesizer's noise per chunk
+        (VC.pipeline).  Every stem stays in device memory from the song file to the cover; only the files main.py leaves behind
+        are copied to the host (all of them with keep_files)."""
+        import time
+        from urllib.parse import urlparse
+        if not song_input or not voice_model:
+            raise ValueError("Ensure that the song input field and voice model field is filled.")
+        if urlparse(song_input).scheme == "https":
+            raise ValueError("%s: downloading a song is not part of this pipeline; pass the path of a local audio file" % song_input)
+        song_input = song_input.strip('"')
+        if not os.path.exists(song_input):
+            raise FileNotFoundError(f"{song_input} does not exist.")
+        song_id = get_hash(song_input)
+        song_dir = os.path.join(self.output_dir, song_id)
+        on_gpu = _lib.backend() == "hip"
+        dev = self.mdx_sessions[0].device
+        fetch = _Fetch(on_gpu)
+        self.last_profile = {}
+        t0 = time.perf_counter()
+
+        cached = None
+        if os.path.exists(song_dir):
+            paths = get_audio_paths(song_dir)
+            if not (any(p is None for p in paths) or keep_files):
+                cached = paths
+        else:
+            os.makedirs(song_dir)
+        if cached is None:
+            orig_song_path, inst_path, dereverb_path, backup_path, inst, backup, dereverb = self._separate(song_input, song_dir,
+                                                                                                          keep_files, fetch)
+            inst_sr = backup_sr = 44100
+        else:
+            orig_song_path, inst_path, dereverb_path, backup_path = cached
+            (inst, inst_sr), (backup, backup_sr), (dereverb, _) = [
+                (torch.from_numpy(np.ascontiguousarray(d)).to(dev), sr) for d, sr in map(read_pcm16, (inst_path, backup_path, dereverb_path))]
+        t0 = self._mark("separate_s", t0)
+
+        pitch_change = pitch_change * 12 + pitch_change_all
+        base = os.path.splitext(os.path.basename(orig_song_path))[0]
+        hop = "" if f0_method != "mangio-crepe" else f"_{crepe_hop_length}"
+        ai_vocals_path = os.path.join(song_dir, f"{base}_{voice_model}_p{pitch_change}_i{index_rate}_fr{filter_radius}_rms{rms_mix_rate}"
+                                                f"_pro{protect}_{f0_method}{hop}.wav")
+        ai_cover_path = os.path.join(song_dir, f"{base} ({voice_model} Ver).{output_format}")
+
+        # the backing stems' pitch shift does not depend on the conversion: one persistent workgroup per stem, queued on a side stream
+        # before the conversion starts and joined before the mix
+        shifted = {}
+        if pitch_change_all != 0:
+            main_stream = torch.cuda.current_stream() if on_gpu else _NoStream()
+            side = torch.cuda.Stream() if on_gpu else _NoStream()
+            side.wait_stream(main_stream)
+            with (torch.cuda.stream(side) if on_gpu else side):
+                for key, pcm, sr, src in (("inst", inst, inst_sr, inst_path), ("backup", backup, backup_sr, backup_path)):
+                    out_path = f"{os.path.splitext(src)[0]}_p{pitch_change_all}.wav"
+                    if os.path.exists(out_path):                                    # main.py:140: an existing file is used as it is
+                        y = torch.from_numpy(np.ascontiguousarray(read_pcm16(out_path)[0])).to(dev)
+                    else:
+                        y = ops.fx_to_pcm16(pitch_shift_signal(_planar(pcm), sr, pitch_change_all)[0])
+                        if keep_files:
+                            fetch.add(write_pcm16, out_path, y, sr)
+                    if on_gpu:
+                        pcm.record_stream(side)
+                        y.record_stream(main_stream)
+                    shifted[key] = y
+
+        if os.path.exists(ai_vocals_path):                                          # main.py:289
+            ai, ai_sr = read_pcm16(ai_vocals_path)
+            ai = torch.from_numpy(np.ascontiguousarray(ai)).to(dev)
+        else:
+            ai, ai_sr = self._convert(voice_model, dereverb, dereverb_path, pitch_change, f0_method, index_rate, filter_radius,
+                                      rms_mix_rate, protect, crepe_hop_length, noise_seed)
+            fetch.add(_write_wavfile, ai_vocals_path, ai, ai_sr)
+            ai = ai.view(-1, 1)
+        t0 = self._mark("convert_s", t0)
+
+        y, _ = vocal_effects(_planar(ai), ai_sr, reverb_rm_size, reverb_wet, reverb_dry, reverb_damping)
+        mixed = ops.fx_to_pcm16(y)
+        if keep_files:
+            fetch.add(write_pcm16, f"{os.path.splitext(ai_vocals_path)[0]}_mixed.wav", mixed, ai_sr)
+        t0 = self._mark("effects_s", t0)
+
+        if pitch_change_all != 0:
+            main_stream.wait_stream(side)
+            inst, backup = shifted["inst"], shifted["backup"]
+        out, sr = mix_stems(mixed, ai_sr, backup, backup_sr, inst, inst_sr, main_gain, backup_gain, inst_gain)
+        fetch.add(lambda p, pcm, r: export(pcm, r, p, output_format), ai_cover_path, out, sr)
+        t0 = self._mark("pitch_join_and_mix_s", t0)
+        fetch.flush()
+        self._mark("files_s", t0)
+        return ai_cover_path
+
+
+_default_session = None
+
+
+def default_session(mdxnet_models_dir=None, rvc_models_dir=None, output_dir=None):
+    """The session behind the module-level song_cover_pipeline: main.py's directories next to the package unless named; made on first
+    use and kept while the directories stay the same."""
+    global _default_session
+    dirs = (mdxnet_models_dir or os.path.join(BASE_DIR, "mdxnet_models"), rvc_models_dir or os.path.join(BASE_DIR, "rvc_models"),
+            output_dir or os.path.join(BASE_DIR, "song_output"))
+    s = _default_session
+    if s is None or (s.mdxnet_models_dir, s.rvc_models_dir, s.output_dir) != dirs:
+        _default_session = CoverSession(*dirs)
+    return _default_session
+
+
+def song_cover_pipeline(song_input, voice_model, pitch_change, keep_files, **kwargs):
+    """CoverSession.song_cover_pipeline on the default session."""
+    return default_session().song_cover_pipeline(song_input, voice_model, pitch_change, keep_files, **kwargs)
+
+
+def build_parser():
+    """main.py's command line (src/main.py:320-339: same flags, same defaults) plus the three directories."""
+    import argparse
+    p = argparse.ArgumentParser(description="Generate a AI cover song in the song_output/id directory.", add_help=True)
+    p.add_argument("-i", "--song-input", type=str, required=True, help="Filepath to a local audio file to create an AI cover of")
+    p.add_argument("-dir", "--rvc-dirname", type=str, required=True, help="Name of the folder in the rvc_models directory containing the RVC model file and optional index file to use")
+    p.add_argument("-p", "--pitch-change", type=int, required=True, help="Change the pitch of AI Vocals only. Generally, use 1 for male to female and -1 for vice-versa. (Octaves)")
+    p.add_argument("-k", "--keep-files", action=argparse.BooleanOptionalAction, help="Whether to keep all intermediate audio files generated in the song_output/id directory")
+    p.add_argument("-ir", "--index-rate", type=float, default=0.5, help="How much of the retrieved features to mix in (0 to 1)")
+    p.add_argument("-fr", "--filter-radius", type=int, default=3, help="Median filtering radius of the harvested pitch (0 to 7)")
+    p.add_argument("-rms", "--rms-mix-rate", type=float, default=0.25, help="How much to use the original vocal's loudness (0) or a fixed loudness (1)")
+    p.add_argument("-palgo", "--pitch-detection-algo", type=str, default="rmvpe", help="rmvpe or mangio-crepe")
+    p.add_argument("-hop", "--crepe-hop-length", type=int, default=128, help="Hop length of mangio-crepe")
+    p.add_argument("-pro", "--protect", type=float, default=0.33, help="Protection of voiceless consonants and breath sounds (0.5 disables it)")
+    p.add_argument("-mv", "--main-vol", type=int, default=0, help="Volume change for AI main vocals in decibels")
+    p.add_argument("-bv", "--backup-vol", type=int, default=0, help="Volume change for backup vocals in decibels")
+    p.add_argument("-iv", "--inst-vol", type=int, default=0, help="Volume change for instrumentals in decibels")
+    p.add_argument("-pall", "--pitch-change-all", type=int, default=0, help="Change the pitch/key of vocals and instrumentals (semitones)")
+    p.add_argument("-rsize", "--reverb-size", type=float, default=0.15, help="Reverb room size between 0 and 1")
+    p.add_argument("-rwet", "--reverb-wetness", type=float, default=0.2, help="Reverb wet level between 0 and 1")
+    p.add_argument("-rdry", "--reverb-dryness", type=float, default=0.8, help="Reverb dry level between 0 and 1")
+    p.add_argument("-rdamp", "--reverb-damping", type=float, default=0.7, help="Reverb damping between 0 and 1")
+    p.add_argument("-oformat", "--output-format", type=str, default="mp3", help="Output format of audio file. mp3 for smaller file size, wav for best quality")
+    p.add_argument("--mdx-models-dir", type=str, default=os.path.join(BASE_DIR, "mdxnet_models"), help="Directory of the MDX-Net .onnx files and model_data.json")
+    p.add_argument("--rvc-models-dir", type=str, default=os.path.join(BASE_DIR, "rvc_models"), help="Directory of hubert_base.pt, rmvpe.pt and the voice model folders")
+    p.add_argument("--output-dir", type=str, default=os.path.join(BASE_DIR, "song_output"), help="Directory the song_id folders are made in")
+    return p
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    if not os.path.exists(os.path.join(args.rvc_models_dir, args.rvc_dirname)):
+        raise Exception(f"The folder {os.path.join(args.rvc_models_dir, args.rvc_dirname)} does not exist.")
+    session = CoverSession(args.mdx_models_dir, args.rvc_models_dir, args.output_dir)
+    cover_path = session.song_cover_pipeline(
+        args.song_input, args.rvc_dirname, args.pitch_change, args.keep_files, main_gain=args.main_vol, backup_gain=args.backup_vol,
+        inst_gain=args.inst_vol, index_rate=args.index_rate, filter_radius=args.filter_radius, rms_mix_rate=args.rms_mix_rate,
+        f0_method=args.pitch_detection_algo, crepe_hop_length=args.crepe_hop_length, protect=args.protect,
+        pitch_change_all=args.pitch_change_all, reverb_rm_size=args.reverb_size, reverb_wet=args.reverb_wetness,
+        reverb_dry=args.reverb_dryness, reverb_damping=args.reverb_damping, output_format=args.output_format)
+    print(f"[+] Cover generated at {cover_path}")
+    return cover_path
+
+
+if __name__ == "__main__":
+    main()

@@ -308,6 +308,37 @@ def run_mdx(model_params, output_dir, model_path, filename, exclude_main=False, 
     return main_filepath, invert_filepath
 
 
+def _run_mdx_placement():
+    """(device, m_threads) as run_mdx chooses them: cuda:0 when there is one, and the reference's segment count by card memory."""
+    device = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
+    vram_gb = torch.cuda.get_device_properties(device).total_memory / 1024 ** 3
+    return device, (2 if vram_gb >= 8 else 1)
+
+
+def load_session(model_params, model_path):
+    """The MDX session run_mdx builds for every call (model hash -> `model_params` entry -> MDXModel -> MDX), to be kept and handed
+    to run_mdx_device: the .onnx is decoded and its weight images are packed once."""
+    device, _ = _run_mdx_placement()
+    entry = model_params.get(MDX.get_hash(model_path))
+    if entry is None:
+        raise KeyError("%s: its hash %s has no entry in model_data.json" % (model_path, MDX.get_hash(model_path)))
+    model = MDXModel(device, dim_f=entry["mdx_dim_f_set"], dim_t=2 ** entry["mdx_dim_t_set"], n_fft=entry["mdx_n_fft_scale_set"],
+                     stem_name=entry["primary_stem"], compensation=entry["compensate"])
+    return MDX(model_path, model)
+
+
+def run_mdx_device(session, stem, denoise, exclude_main=False, exclude_inversion=False, group=None):
+    """run_mdx between its file read and its file writes, on device tensors: `stem` is the previous stage's (frames, C) int16 PCM
+    or the (C, n) float32 signal audio_io.load_wav returns (C = 1 or 2), resident where `session` runs.  Returns
+    (main_pcm | None, inverted_pcm | None), (n, 2) int16 device tensors holding the samples run_mdx writes to its two files.
+    ops.stem_normalise -> dist.mdx_separate -> ops.mdx_stems_pcm16; the peak stays on the device and the host waits for nothing."""
+    from . import dist as adist
+    _, m_threads = _run_mdx_placement()
+    wave, peak = ops.stem_normalise(stem)
+    separated = adist.mdx_separate(session, wave, denoise, m_threads, group)
+    return ops.mdx_stems_pcm16(wave, separated.contiguous(), peak, session.model.compensation, not exclude_main, not exclude_inversion)
+
+
 def run_mdx_arrays(mdx_sess, wave, denoise, m_threads=2, group=None):
     """The array-level core of run_mdx: normalised (2, N) numpy in -> separated (2, N) numpy out.  With a
     torch.distributed `group` (or an initialised default group) the window list is sharded across ranks and joined

@@ -1070,6 +1070,49 @@ def pcm16_mix(a, a_rate, a_gains, b, b_rate, b_gains, out_frames):
 
 
 # ---------------------------------------------------------------------------------------------------
+# Stems handed from one stage of a cover to the next (csrc/handover.hip): the head and the tail of run_mdx on the device
+# ---------------------------------------------------------------------------------------------------
+STEM_PCM16, STEM_F32 = 0, 1
+
+
+def stem_normalise(x):
+    """x: (frames, C) int16 PCM (read as x / 32768) or (C, n) float32, C = 1 or 2 (mono serves both rows).
+    Returns (wave (2, n) float32 = x / peak, peak (1,) float32 = max(max(x), |min(x)|)), both on x's device: nothing waits for the
+    peak."""
+    if x.dim() != 2:
+        raise ValueError("stem_normalise takes (frames, channels) int16 or (channels, n) float32, got %s" % (tuple(x.shape),))
+    if not x.is_contiguous():
+        raise ValueError("stem_normalise takes a contiguous tensor (strides %s of shape %s)" % (x.stride(), tuple(x.shape)))
+    fmt = {torch.int16: STEM_PCM16, torch.float32: STEM_F32}.get(x.dtype, -1)   # any other dtype: the library names what it reads
+    n, C = (x.shape[1], x.shape[0]) if fmt == STEM_F32 else (x.shape[0], x.shape[1])
+    out = torch.empty((2, n), dtype=torch.float32, device=x.device)
+    peak = torch.empty(1, dtype=torch.float32, device=x.device)
+    _check(x)
+    _call("aicg_stem_normalise", _ptr(x), fmt, C, n, _ptr(out), _ptr(peak), _stream(x))
+    return out, peak
+
+
+def mdx_stems_pcm16(wave, separated, peak, compensation, want_main=True, want_inverted=True):
+    """wave (the normalised input), separated: (2, n) float32; peak: (1,) float32 on the device.  Returns (main, inverted): (n, 2)
+    int16 of separated * peak and of wave - (separated * peak) * compensation, None for a stem that is not wanted."""
+    for t in (wave, separated):
+        if t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] != 2:
+            raise TypeError("mdx_stems_pcm16 takes (2, n) float32 signals, got %s %s" % (t.dtype, tuple(t.shape)))
+        if not t.is_contiguous():
+            raise ValueError("mdx_stems_pcm16 takes contiguous tensors (strides %s of shape %s)" % (t.stride(), tuple(t.shape)))
+    if wave.shape != separated.shape:
+        raise ValueError("mdx_stems_pcm16: wave %s and separated %s differ in shape" % (tuple(wave.shape), tuple(separated.shape)))
+    if peak.dtype != torch.float32 or peak.numel() != 1:
+        raise TypeError("mdx_stems_pcm16: peak is one float32 on the device, got %s %s" % (peak.dtype, tuple(peak.shape)))
+    n = wave.shape[1]
+    main = torch.empty((n, 2), dtype=torch.int16, device=wave.device) if want_main else None
+    inv = torch.empty((n, 2), dtype=torch.int16, device=wave.device) if want_inverted else None
+    _check(wave, separated, peak)
+    _call("aicg_mdx_stems_pcm16", _ptr(wave), _ptr(separated), _ptr(peak), float(compensation), n, _ptr(main), _ptr(inv), _stream(wave))
+    return main, inv
+
+
+# ---------------------------------------------------------------------------------------------------
 # Pitch shift of the backing stems (csrc/pitch.hip): WSOLA time-stretch, then resampling by an irrational ratio
 # ---------------------------------------------------------------------------------------------------
 def tempo_wsola_geometry(sr, tempo, n):

@@ -691,8 +691,9 @@ class VC(object):
         if c.on_gpu:
             torch.cuda.synchronize()
 
-    def _post(self, audio_opt, audio, tgt_sr, resample_sr, rms_mix_rate):
-        """The joined float32 track at tgt_sr -> the call's int16 result: RMS mix with the input, peak limit, truncating cast (reference :639-651)."""
+    def _post(self, audio_opt, audio, tgt_sr, resample_sr, rms_mix_rate, device_out=False):
+        """The joined float32 track at tgt_sr -> the call's int16 result: RMS mix with the input, peak limit, truncating cast (reference :639-651).
+        `device_out`: the int16 tensor stays on the device (the same samples) instead of being copied to a host array."""
         if resample_sr >= 16000 and tgt_sr != resample_sr:
             # optional output resampling (rvc_infer passes resample_sr=0): host fallback, not on the hot path
             a = audio_opt.cpu().numpy()
@@ -709,13 +710,15 @@ class VC(object):
         max_int16 = 32768
         if audio_max > 1:
             max_int16 /= audio_max
-        return ops.to_int16(audio_opt, max_int16).cpu().numpy()
+        out = ops.to_int16(audio_opt, max_int16)
+        return out if device_out else out.cpu().numpy()
 
     @_bracket_pipeline
     def pipeline(self, model, net_g, sid, audio, input_audio_path, times, f0_up_key, f0_method, file_index, index_rate,
                  if_f0, filter_radius, tgt_sr, resample_sr, rms_mix_rate, version, protect, crepe_hop_length, f0_file=None,
-                 noise_fn=None, group=None, noise_seed=None):
-        """Same contract as the reference (:474-653): float32 16 kHz mono in, int16 at tgt_sr out.
+                 noise_fn=None, group=None, noise_seed=None, device_out=False):
+        """Same contract as the reference (:474-653): float32 16 kHz mono in, int16 at tgt_sr out (`device_out`: as an int16 tensor left
+        on the device, for a caller that goes on there; the samples are the same).
         `noise_fn(chunk_index, start, end) -> (noise_z, noise_src)` injects the synthesizer noise (tests); `noise_seed`
         instead draws it from a per-chunk seeded device generator, which makes the output independent of how chunks are
         distributed over ranks UP TO fp32 SUMMATION ORDER: the HuBERT transformer runs once over all of a rank's chunks
@@ -747,7 +750,8 @@ class VC(object):
         tc1 = ttime()
         pieces = adist.gather_pieces(c.pieces, len(bounds), self.device, group)
         tj1 = ttime()
-        audio_opt = self._post(torch.cat([pieces[i] for i in range(len(bounds))]).contiguous(), audio, tgt_sr, resample_sr, rms_mix_rate)
+        audio_opt = self._post(torch.cat([pieces[i] for i in range(len(bounds))]).contiguous(), audio, tgt_sr, resample_sr, rms_mix_rate,
+                               device_out)
         # wall-clock split of this call (host pre-processing, f0, chunk loop, join + host post-processing)
         # (overlapped schedule: f0_s = features of every chunk with the f0 branch underneath, f0_wait_s of it spent waiting for f0)
         self.last_profile = {"plan_s": t1 - tp0, "f0_s": c.t2 - t1, "chunks_s": tc1 - c.t2, "post_s": ttime() - tc1,

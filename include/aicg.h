@@ -441,6 +441,26 @@ int aicg_tempo_wsola(const float* x, float* y, int* offsets_out, const int* offs
 int aicg_resample_ratio(const float* x, float* y, int n_signals, int n_channels, int64_t n_in, int64_t n_out, double ratio,
                         const float* table, int phases, int half_taps, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Stems handed from one stage of a cover to the next in device memory (csrc/handover.hip): the head and the tail of run_mdx
+ * without the WAV file in between.  numpy rounds after every operation of the lines named here; so do these (no contraction, IEEE
+ * division).
+ *
+ * aicg_stem_normalise: src/mdx.py:257-259 (`wave, sr = librosa.load(...)`; the mono duplication; `peak = max(np.max(wave),
+ *   abs(np.min(wave)))`; `wave /= peak`).  x is in_format 0: 16-bit PCM [n][n_channels] read as x / 32768, or in_format 1: fp32
+ *   [n_channels][n]; n_channels = 1 or 2, one channel serves both rows.  out [2][n] = wave / peak; *peak (device memory) receives
+ *   the peak, so the host never waits for it.  peak = 0 divides by zero as numpy does; NaN samples are skipped by the peak (np.max returns them) and
+ *   become -32768 in aicg_mdx_stems_pcm16.  x and out are 16-byte aligned.
+ * aicg_mdx_stems_pcm16: src/mdx.py:264-280 (`* peak`; `sf.write(main_filepath, wave_processed.T, sr)`; `sf.write(invert_filepath,
+ *   (-wave_processed.T * compensation) + wave.T, sr)`).  wave, separated: fp32 [2][n] (wave is the NORMALISED input, as in the
+ *   reference); s = separated * *peak; main_out [n][2] = pcm16(s); inverted_out [n][2] = pcm16(wave - s * compensation) with
+ *   pcm16(y) = rint(clip(y, -1, 32767 / 32768) * 32768), ties to even (libsndfile's 16-bit PCM of a float).  Either output may be
+ *   NULL (exclude_main / exclude_inversion), not both; outputs are 16-byte aligned.
+ * ---------------------------------------------------------------------------------------------- */
+int aicg_stem_normalise(const void* x, int in_format, int n_channels, int64_t n, float* out, float* peak, void* stream);
+int aicg_mdx_stems_pcm16(const float* wave, const float* separated, const float* peak, float compensation, int64_t n,
+                         int16_t* main_out, int16_t* inverted_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

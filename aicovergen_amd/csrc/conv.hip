@@ -124,6 +124,8 @@ namespace {
 struct ConvCall {
     const aicg_conv_desc* d;
     int pad_h_end, pad_w_end;   // the descriptor's end paddings, resolved (negative there: the leading ones)
+    long plan_w, plan_wo;       // row lengths (input, output) the tile policies count with: the real ones, or those of the uncropped
+                                // problem this launch is a window of (aicg_conv_forward_planned)
     hipStream_t st;
 };
 
@@ -324,7 +326,7 @@ int route_g1(ConvArgs& p, const ConvCall& c) {
     AICG_SWITCH(g1env, "AICG_CONV_G1", 0);
     const long g1 = c.d->gemm_tile ? c.d->gemm_tile : g1env;
     if (!(g1 != 1 && !p.wsplit && p.Cout_g > 32 && conv_g1_applicable(p, c.pad_h_end, c.pad_w_end))) return 1;
-    const long HW = (long)p.H * p.W;
+    const long HW = (long)p.H * c.plan_w;
     const int M = p.Cout_g;
     auto wgs = [&](int bm) { return (long)p.N * idiv_up(M, bm) * ldiv_up(HW, 256); };
     if (p.f16 && !p.shuffle) {
@@ -366,7 +368,7 @@ int route_g1(ConvArgs& p, const ConvCall& c) {
 int route_g1s(ConvArgs& p, const ConvCall& c) {
     const int tile = c.d->gemm_tile;
     if (!(tile != 1 && !p.wsplit && p.Cout_g > 32 && conv_g1s_applicable(p, c.pad_w_end))) return 1;
-    const long w64 = (long)p.N * idiv_up(p.Cout_g, 64) * idiv_up(p.Wo, 256);
+    const long w64 = (long)p.N * idiv_up(p.Cout_g, 64) * ldiv_up(c.plan_wo, 256);
     if (tile == 2) return run_g1s_128x256(p, c.st);
     if (tile == 3 || w64 >= 160) return run_g1s_64x256(p, c.st);
     return 1;
@@ -406,7 +408,7 @@ TilePlan plan_tiles(ConvArgs& p, const ConvCall& c) {
     AICG_SWITCH(force_bm, "AICG_CONV_FORCE_BM", 0);
     if (force_bm) t.BM = (int)force_bm;
     t.groups = p.groups;
-    t.npos = (long)p.N * p.Ho * p.Wo;
+    t.npos = (long)p.N * p.Ho * c.plan_wo;
     t.st = c.st;
     AICG_SWITCH(ablate, "AICG_CONV_ABLATE", 0);
     p.dbg = ablate;
@@ -554,9 +556,18 @@ int route_single_role(ConvArgs& p, const TilePlan& t) {
 
 extern "C" int aicg_conv_forward(const aicg_conv_desc* d, const float* x, const float* w_packed, const float* bias,
                                  const float* res, float* y, void* stream) {
+    return aicg_conv_forward_planned(d, x, w_packed, bias, res, y, 0, stream);
+}
+
+extern "C" int aicg_conv_forward_planned(const aicg_conv_desc* d, const float* x, const float* w_packed, const float* bias,
+                                         const float* res, float* y, int plan_w, void* stream) {
     ConvCall c;
     int rc = validate_desc(d, x, w_packed, res, y, c);
     if (rc <= 0) return rc;
+    if (plan_w && plan_w < d->W) return fail(AICG_E_SHAPE, "aicg_conv_forward_planned: plan_w %d is shorter than the map (%d)", plan_w, d->W);
+    // the uncropped problem: plan_w input columns, and as many more output columns as the crop removed input columns per stride
+    c.plan_w = plan_w ? plan_w : d->W;
+    c.plan_wo = d->Wo + (c.plan_w - d->W) / d->stride_w;
     c.st = (hipStream_t)stream;
     ConvArgs p;
     fill_args(p, d, x, w_packed, bias, res, y);

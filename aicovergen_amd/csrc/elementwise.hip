@@ -126,15 +126,23 @@ __global__ void __launch_bounds__(256) sine_frame_prefix_kernel(const float* __r
 // One thread = FOUR consecutive samples of one frame (upp % 4 == 0: 400 / 480 / 320 of the 40k / 48k / 32k models): one float4 of
 // noise in, one float4 out, the frame's f0 / prefix / rad read once.  (r3: one sample per thread, scalar loads and stores, 3 % of the
 // HBM rate; what remains of the time is the two launches and the scan above -- 21 MB per chunk are a 4 us stream.)
+// Both kernels write a WINDOW of the T upp samples: out[j] = sample first + j, j < count, zero where that lies outside the signal (the
+// whole signal is the window first = 0, count = T upp -- one code for both, so a window has the bits of the whole).  Here first and
+// count are multiples of four.
 __global__ void __launch_bounds__(256) sine_source4_kernel(const float* __restrict__ f0, const double* __restrict__ prefix,
                                                            const float* __restrict__ noise, float* __restrict__ out,
                                                            int T, int upp, float sr, float sine_amp, float noise_std,
-                                                           float lin_w, float lin_b) {
-    const int q_per = upp >> 2;
-    const long total4 = (long)T * q_per;
+                                                           float lin_w, float lin_b, long first, long count) {
+    const long total = (long)T * upp;
+    const long total4 = count >> 2;
     for (long n4 = (long)blockIdx.x * blockDim.x + threadIdx.x; n4 < total4; n4 += (long)gridDim.x * blockDim.x) {
-        const int t = (int)(n4 / q_per);
-        const int i0 = (int)(n4 - (long)t * q_per) * 4;
+        const long n0 = first + 4 * n4;
+        if (n0 < 0 || n0 >= total) {
+            *reinterpret_cast<float4*>(out + 4 * n4) = make_float4(0.f, 0.f, 0.f, 0.f);
+            continue;
+        }
+        const int t = (int)(n0 / upp);
+        const int i0 = (int)(n0 - (long)t * upp);
         const float f = f0[t];
         const float rad = fmodf(f / sr, 1.0f);
         const double base = prefix[t];
@@ -151,16 +159,21 @@ __global__ void __launch_bounds__(256) sine_source4_kernel(const float* __restri
             const float v = sine * uv + namp * nv[j];
             o[j] = tanhf(lin_w * v + lin_b);  // l_linear (1->1) + tanh (models.py:418)
         }
-        *reinterpret_cast<float4*>(out + (long)t * upp + i0) = make_float4(o[0], o[1], o[2], o[3]);
+        *reinterpret_cast<float4*>(out + 4 * n4) = make_float4(o[0], o[1], o[2], o[3]);
     }
 }
 
 __global__ void __launch_bounds__(256) sine_source_kernel(const float* __restrict__ f0, const double* __restrict__ prefix,
                                                           const float* __restrict__ noise, float* __restrict__ out,
                                                           int T, int upp, float sr, float sine_amp, float noise_std,
-                                                          float lin_w, float lin_b) {
+                                                          float lin_w, float lin_b, long first, long count) {
     const long total = (long)T * upp;
-    for (long n = (long)blockIdx.x * blockDim.x + threadIdx.x; n < total; n += (long)gridDim.x * blockDim.x) {
+    for (long j = (long)blockIdx.x * blockDim.x + threadIdx.x; j < count; j += (long)gridDim.x * blockDim.x) {
+        const long n = first + j;
+        if (n < 0 || n >= total) {
+            out[j] = 0.f;
+            continue;
+        }
         const int t = (int)(n / upp);
         const int i = (int)(n - (long)t * upp);
         const float f = f0[t];
@@ -171,7 +184,7 @@ __global__ void __launch_bounds__(256) sine_source_kernel(const float* __restric
         const float uv = f > 0.f ? 1.f : 0.f;
         const float namp = uv * noise_std + (1.f - uv) * sine_amp / 3.f;
         const float v = sine * uv + namp * noise[n];
-        out[n] = tanhf(lin_w * v + lin_b);  // l_linear (1->1) + tanh (models.py:418)
+        out[j] = tanhf(lin_w * v + lin_b);  // l_linear (1->1) + tanh (models.py:418)
     }
 }
 
@@ -273,10 +286,35 @@ extern "C" int aicg_sine_source(const float* f0, const float* noise, double* pre
     hipLaunchKernelGGL(sine_frame_prefix_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, f0, prefix_scratch, T, upp, sr);
     if ((upp & 3) == 0 && ((uintptr_t)noise & 15) == 0 && ((uintptr_t)out & 15) == 0)
         hipLaunchKernelGGL(sine_source4_kernel, dim3(ew_grid((long)T * (upp >> 2))), dim3(256), 0, (hipStream_t)stream, f0,
-                           (const double*)prefix_scratch, noise, out, T, upp, sr, sine_amp, noise_std, lin_w, lin_b);
+                           (const double*)prefix_scratch, noise, out, T, upp, sr, sine_amp, noise_std, lin_w, lin_b, 0L, (long)T * upp);
     else
         hipLaunchKernelGGL(sine_source_kernel, dim3(ew_grid((long)T * upp)), dim3(256), 0, (hipStream_t)stream, f0,
-                           (const double*)prefix_scratch, noise, out, T, upp, sr, sine_amp, noise_std, lin_w, lin_b);
+                           (const double*)prefix_scratch, noise, out, T, upp, sr, sine_amp, noise_std, lin_w, lin_b, 0L, (long)T * upp);
+    return check_launch("sine_source_kernel");
+}
+
+extern "C" int aicg_sine_source_window(const float* f0, const float* noise, double* prefix_scratch, float* out, int T, int upp,
+                                       float sr, float sine_amp, float noise_std, float lin_w, float lin_b, int64_t first,
+                                       int64_t count, void* stream) {
+    if (!f0 || !noise || !prefix_scratch || !out) return fail(AICG_E_ARG, "aicg_sine_source_window: null pointer");
+    if (T < 0 || upp < 1 || count < 0) return fail(AICG_E_SHAPE, "aicg_sine_source_window: bad shape");
+    if (count == 0) return AICG_OK;
+    // a source generated in quads (upp % 4 == 0: sine_source4_kernel) is cut on quads: every sample comes from the same kernel form
+    if ((upp & 3) == 0 && ((first & 3) != 0 || (count & 3) != 0))
+        return fail(AICG_E_ARG, "aicg_sine_source_window: upp %% 4 == 0 needs first and count to be multiples of 4");
+    const long total = (long)T * upp;
+    // frames the window reads: the scan stops behind the last of them
+    const long last = lmin(total, (long)first + (long)count);
+    const int Tscan = last <= 0 ? 0 : (int)((last + upp - 1) / upp);
+    if (Tscan > 0 && first < total)
+        hipLaunchKernelGGL(sine_frame_prefix_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, f0, prefix_scratch, Tscan, upp, sr);
+    // the form aicg_sine_source takes for this upp and noise pointer (its out is the caller's: 16-byte aligned in both calls or neither)
+    if ((upp & 3) == 0 && ((uintptr_t)noise & 15) == 0 && ((uintptr_t)out & 15) == 0)
+        hipLaunchKernelGGL(sine_source4_kernel, dim3(ew_grid((long)count >> 2)), dim3(256), 0, (hipStream_t)stream, f0,
+                           (const double*)prefix_scratch, noise, out, T, upp, sr, sine_amp, noise_std, lin_w, lin_b, (long)first, (long)count);
+    else
+        hipLaunchKernelGGL(sine_source_kernel, dim3(ew_grid((long)count)), dim3(256), 0, (hipStream_t)stream, f0,
+                           (const double*)prefix_scratch, noise, out, T, upp, sr, sine_amp, noise_std, lin_w, lin_b, (long)first, (long)count);
     return check_launch("sine_source_kernel");
 }
 

@@ -263,29 +263,123 @@ class _SynthesizerBase:
             ops.conv(out, Fl["post_neg"], res=x1, out=x1)  # x1 <- x1 - (post(h))   (mean-only coupling)
         return z
 
-    def _decoder(self, P, x, f0, g, noise_src):
-        """GeneratorNSF.forward / Generator.forward (models.py:494-516, 253-272)."""
+    # ---- the decoder's receptive field, and the window of frames a kept range of output needs ------------------------
+    def _decoder_geometry(self):
+        """Kernel sizes the constructor does not carry, read off the loaded weights: (conv_pre k, conv_post k, [noise conv k per stage])."""
+        sd = self._sd
+        assert sd is not None, "load_state_dict() first"
+        noise = [sd["dec.noise_convs.%d.weight" % i].shape[2] for i in range(len(self.upsample_rates))] if self.use_f0 else []
+        return sd["dec.conv_pre.weight"].shape[2], sd["dec.conv_post.weight"].shape[2], noise
+
+    def decoder_reach(self):
+        """How many frames of z (and of f0) on either side of a frame-aligned range of output samples that range depends on, rounded up --
+        derived from the layers' geometry alone, as E2E.time_reach() is for RMVPE.  Walked backwards from the waveform, r = the reach in
+        samples at the running stage's rate: conv_post (k - 1) / 2; per stage the longest ResBlock chain (ResBlock1: per dilation d the
+        dilated and the plain convolution, (k - 1) / 2 (d + 1); ResBlock2: (k - 1) / 2 d), then the transposed convolution, which maps
+        r output samples to floor((r + k - 1 - p) / u) inputs on the left and ceil((r + p) / u) on the right (p = (k - u) / 2: output
+        o = i u - p + tap); finally conv_pre.  The harmonic source enters every stage through its noise convolution (kernel kn, stride s,
+        padding pn at the source's rate): r outputs there reach r s + max(pn, kn - s - pn) source samples; a source sample depends on the f0
+        of its own frame (and, through the phase, on the f0 of every EARLIER frame: that is carried exactly, not cropped).
+        -> (frames, frames of z alone, source samples): (11, 11, 2860) for the 40k v2 model (10, 10, 2, 2; ResBlock1 3 / 7 / 11, 1 / 3 / 5)."""
+        k_pre, k_post, k_noise = self._decoder_geometry()
+        ups, uks = self.upsample_rates, self.upsample_kernel_sizes
+
+        def chain(k, dil):
+            h = (k - 1) // 2
+            return sum(h * d + (h if self.resblock == "1" else 0) for d in dil)
+        rb = max(chain(k, d) for k, d in zip(self.resblock_kernel_sizes, self.resblock_dilation_sizes))
+        r = (k_post - 1) // 2
+        src = 0
+        for i in reversed(range(len(ups))):
+            r += rb
+            if self.use_f0:
+                s = int(np.prod(ups[i + 1:]))
+                kn, pn = k_noise[i], (s // 2 if i + 1 < len(ups) else 0)
+                src = max(src, r * s + max(pn, kn - s - pn))
+            u, k = ups[i], uks[i]
+            p = (k - u) // 2
+            r = max((r + k - 1 - p) // u, -(-(r + p) // u))
+        r += (k_pre - 1) // 2
+        return max(r, -(-src // self.upp)), r, src
+
+    def decoder_granule(self):
+        """Frames by which a cropped decoder run may start later than the full one with every kept sample on the SAME arithmetic path.
+        The direct kernels (implicit GEMM, col2im, the streaming layers) sum an output's products in an order that does not depend on
+        where the output sits in its tile; the Winograd form F(2, 3) of the ResBlock layers (csrc/conv_g1w.h) computes outputs in pairs
+        (n, n + d) inside blocks of 4 d that start at multiples of the tile (512 outputs for d = 1, 480 for d = 3 and 5): whether an
+        output is the first or the second of its pair -- y = M0 + M1 + M2 or M1 - M2 - M3 -- depends on n mod 2 d.  So the start,
+        referred to each stage's rate, is a multiple of lcm(4, 2 d for every dilation) -- the 4 keeps rows on the float4 boundaries the
+        kernels' alignment gates ask about -- and, in frames, a multiple of 4 (stage lengths keep their residue mod 4: the same gates
+        open and close).  12 frames for the 40k and 32k v2 models, 20 for 48k v2 (rates 12, 10, 2, 2)."""
+        L = 4
+        for dil in self.resblock_dilation_sizes:
+            for d in dil:
+                L = L * (2 * d) // math.gcd(L, 2 * d)
+        G, rate = 4, 1
+        for u in self.upsample_rates:
+            rate *= u
+            need = L // math.gcd(L, rate)
+            G = G * need // math.gcd(G, need)
+        return G
+
+    def decoder_window(self, T, keep):
+        """keep = (lo, hi): the output samples wanted of a T-frame decode -> the frame range (a0, a1) to run instead, or None where nothing
+        would be saved or the geometry is not the exact-rate one (transposed convolutions with k - u odd).  a0 is rounded down to the
+        granule; a1 leaves a multiple of four frames behind it, so that a1 - a0 = T mod 4."""
+        lo, hi = keep
+        assert 0 <= lo <= hi <= T * self.upp
+        if any((k - u) % 2 for u, k in zip(self.upsample_rates, self.upsample_kernel_sizes)):
+            return None
+        reach, G = self.decoder_reach()[0], self.decoder_granule()
+        a0 = max(0, lo // self.upp - reach) // G * G
+        a1 = T - max(0, T - (-(-hi // self.upp) + reach)) // 4 * 4
+        if (a0 == 0 and a1 == T) or a1 <= a0:
+            return None
+        return a0, a1
+
+    def _decoder(self, P, x, f0, g, noise_src, window=None):
+        """GeneratorNSF.forward / Generator.forward (models.py:494-516, 253-272).  `window` = (a0, a1) (decoder_window): only frames
+        a0 .. a1 - 1 are synthesised -> (1, 1, (a1 - a0) upp); samples further than decoder_reach() from both cuts have the bits of the
+        full run: every layer is told the full row length (plan_w) and keeps its kernel and tile."""
         T = x.shape[2]
+        a0, a1 = (0, T) if window is None else window
+        Tw = a1 - a0
+        plan = (lambda w: None) if window is None else (lambda w: int(w))
         har = None
         if self.use_f0:
             if noise_src is None:
                 noise_src = torch.randn(T * self.upp, device=x.device)  # reference: torch.randn_like (models.py:368)
-            har = ops.sine_source(f0.reshape(-1)[:T], noise_src.to(x.device).reshape(-1), self.upp, float(self.sr), P["lin_w"], P["lin_b"])
+            if window is None:
+                halo = 0
+                har = ops.sine_source(f0.reshape(-1)[:T], noise_src.to(x.device).reshape(-1), self.upp, float(self.sr), P["lin_w"], P["lin_b"])
+            else:
+                # the window's source with the noise convolutions' widest padding on either side (real samples inside the chunk, zeros
+                # beyond its ends), in whole quads: a stage's padded source is a slice of it
+                halo = -(-max(s // 2 for s, _ in P["noise"]) // 4) * 4
+                har = ops.sine_source_window(f0.reshape(-1)[:T], noise_src.to(x.device).reshape(-1), self.upp, float(self.sr), P["lin_w"],
+                                             P["lin_b"], a0 * self.upp - halo, Tw * self.upp + 2 * halo)
+                x = x[:, :, a0:a1].contiguous()
+        elif window is not None:
+            x = x[:, :, a0:a1].contiguous()
         pre_bias = ops.conv(g, P["cond"], res=P["conv_pre_bias"])  # conv_pre.bias + cond(g), per-channel constant
-        x = ops.conv(x, P["conv_pre"], bias=pre_bias.reshape(-1))
+        x = ops.conv(x, P["conv_pre"], bias=pre_bias.reshape(-1), plan_w=plan(T))
         nk = len(self.resblock_kernel_sizes)
+        rate = 1
         for i, pt in enumerate(P["ups"]):
             add = None
             if har is not None:
                 s, nc = P["noise"][i]
-                L = har.numel()
+                L, Lfull = Tw * self.upp, T * self.upp
                 if s > 1:
-                    xp = F.pad(har, (s // 2, s // 2))                     # zero padding of Conv1d(padding=s//2)
+                    # zero padding of Conv1d(padding=s//2)
+                    xp = F.pad(har, (s // 2, s // 2)) if window is None else har[halo - s // 2: halo + L + s // 2]
                     phases = xp.view(L // s + 1, s).t().contiguous()      # X[ph][q] = xpad[q*s + ph]
-                    add = ops.conv(phases.unsqueeze(0), nc)
+                    add = ops.conv(phases.unsqueeze(0), nc, plan_w=plan(Lfull // s + 1))
                 else:
-                    add = ops.conv(har.view(1, 1, L), nc)
-            x = ops.conv_transpose(x, pt, add=add, pre_act=ops.ACT_LRELU, pre_slope=LRELU_SLOPE)
+                    add = ops.conv(har[halo: halo + L].view(1, 1, L), nc, plan_w=plan(Lfull))
+            x = ops.conv_transpose(x, pt, add=add, pre_act=ops.ACT_LRELU, pre_slope=LRELU_SLOPE, plan_w=plan(T * rate))
+            rate *= self.upsample_rates[i]
+            pw = plan(T * rate)
             acc = torch.empty_like(x)
             # The num_kernels ResBlocks of a stage read the same x and are independent up to their last convolution, which adds into
             # the shared sum (models.py:506-512).  Opt-in (AICG_RB_STREAMS=1): each chain on its own stream, so that a launch's ragged
@@ -318,25 +412,25 @@ class _SynthesizerBase:
                         else:
                             # c2 reads c1's output only through the leaky ReLU (modules.py:305-309): c1's epilogue applies it once per
                             # element (same multiplication, same bits) and c2 runs without an input activation
-                            ops.conv(y, c1, out=tmp, pre_act=ops.ACT_LRELU, pre_slope=LRELU_SLOPE, act=ops.ACT_LRELU, act_slope=LRELU_SLOPE)
+                            ops.conv(y, c1, out=tmp, pre_act=ops.ACT_LRELU, pre_slope=LRELU_SLOPE, act=ops.ACT_LRELU, act_slope=LRELU_SLOPE, plan_w=pw)
                             src, inp = c2, tmp
                         if last:  # xs += resblock(x); x = xs / num_kernels  (models.py:506-512)
                             if streams and prev_acc is not None:
                                 st.wait_event(prev_acc)
                             pre = ops.ACT_NONE if c2 is not None else ops.ACT_LRELU
-                            ops.conv(inp, src, res=y, out=acc, pre_act=pre, pre_slope=LRELU_SLOPE, out_scale=1.0 / nk, accumulate=j > 0)
+                            ops.conv(inp, src, res=y, out=acc, pre_act=pre, pre_slope=LRELU_SLOPE, out_scale=1.0 / nk, accumulate=j > 0, plan_w=pw)
                             if streams:
                                 prev_acc = torch.cuda.Event()
                                 prev_acc.record(st)
                         else:
                             dst = ya if y is not ya else yb
-                            ops.conv(inp, src, res=y, out=dst, pre_act=ops.ACT_NONE if c2 is not None else ops.ACT_LRELU, pre_slope=LRELU_SLOPE)
+                            ops.conv(inp, src, res=y, out=dst, pre_act=ops.ACT_NONE if c2 is not None else ops.ACT_LRELU, pre_slope=LRELU_SLOPE, plan_w=pw)
                             y = dst
             if streams:
                 main.wait_event(prev_acc)
             x = acc
         # F.leaky_relu default slope 0.01 (models.py:513), conv_post (no bias), tanh
-        return ops.conv(x, P["conv_post"], pre_act=ops.ACT_LRELU, pre_slope=0.01, act=ops.ACT_TANH)
+        return ops.conv(x, P["conv_post"], pre_act=ops.ACT_LRELU, pre_slope=0.01, act=ops.ACT_TANH, plan_w=plan(T * rate))
 
     def _rb_streams(self, device, nk):
         """Side streams for the ResBlock chains of a vocoder stage (one per chain but the first, created once per model: the caching
@@ -349,10 +443,10 @@ class _SynthesizerBase:
         return have
 
     def infer(self, phone, phone_lengths, pitch=None, nsff0=None, sid=None, max_len=None, noise_z=None, noise_src=None,
-              phone_ct=None):
+              phone_ct=None, keep=None):
         """Same contract as the reference (models.py:745-751).  `noise_z` (1, inter, T) and `noise_src` (T*upp)
         optionally replace the two torch.randn_like draws (parity tests inject them on both sides).  `phone_ct`
-        (1, phone_dim, T) passes the features already channel-major (what aicg_feats_prepare writes)."""
+        (1, phone_dim, T) passes the features already channel-major (what aicg_feats_prepare writes).  `keep`: see infer_back."""
         if not self.use_f0 and sid is None:  # _nono signature: infer(phone, phone_lengths, sid, max_len=None)
             sid, pitch = pitch, None
         P = self._prepare()
@@ -365,7 +459,7 @@ class _SynthesizerBase:
         else:
             T = phone_ct.shape[2]
         front = self.infer_front(phone_ct, pitch, sid, noise_z)
-        return self.infer_back(front, nsff0, noise_src, max_len)
+        return self.infer_back(front, nsff0, noise_src, max_len, keep=keep)
 
     def infer_front(self, phone_ct, pitch, sid, noise_z=None):
         """First half of infer(): speaker embedding, text encoder, prior sample, reverse flow -> state for infer_back.  A few
@@ -382,13 +476,24 @@ class _SynthesizerBase:
         z = self._flow_reverse(P, z_p.clone(), g)
         return {"z": z, "z_p": z_p, "stats": stats, "g": g, "T": T}
 
-    def infer_back(self, front, nsff0=None, noise_src=None, max_len=None):
-        """Second half of infer(): the (NSF-)HiFiGAN vocoder on the flow's output -> (o, x_mask, (z, z_p, m_p, logs_p))."""
+    def infer_back(self, front, nsff0=None, noise_src=None, max_len=None, keep=None):
+        """Second half of infer(): the (NSF-)HiFiGAN vocoder on the flow's output -> (o, x_mask, (z, z_p, m_p, logs_p)).
+        `keep` = (lo, hi): o is only o[:, :, lo:hi] of the full waveform -- the same bits --, and the vocoder runs only the frames those
+        samples depend on (decoder_window; VC.pipeline trims every chunk's padding this way).  Where that saves nothing (the padding no
+        longer than reach plus alignment, a range that covers the chunk) the full waveform is computed and sliced."""
         P = self._prepare()
         dev = self.device
         z, z_p, stats, g, T = front["z"], front["z_p"], front["stats"], front["g"], front["T"]
         zz = z if max_len is None else z[:, :, :max_len].contiguous()
-        o = self._decoder(P, zz, None if nsff0 is None else nsff0.to(dev).float(), g, noise_src)
+        f0 = None if nsff0 is None else nsff0.to(dev).float()
+        if keep is None:
+            o = self._decoder(P, zz, f0, g, noise_src)
+        else:
+            lo, hi = int(keep[0]), int(keep[1])
+            window = self.decoder_window(zz.shape[2], (lo, hi))
+            o = self._decoder(P, zz, f0, g, noise_src, window=window)
+            first = 0 if window is None else window[0] * self.upp
+            o = o[:, :, lo - first: hi - first]
         x_mask = torch.ones((1, 1, T), dtype=torch.float32, device=dev)
         m_p, logs_p = stats[:, : self.inter_channels], stats[:, self.inter_channels:]
         return o, x_mask, (z, z_p, m_p, logs_p)

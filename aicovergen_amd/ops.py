@@ -425,9 +425,11 @@ gemm_tile = 0
 
 
 def conv(x, pc, res=None, out=None, pre_act=ACT_NONE, pre_slope=0.0, act=ACT_NONE, act_slope=0.0, out_scale=1.0,
-         accumulate=False, bias=None, res_before_act=False, out_len=None, shuffle=0, res_mul=False):
+         accumulate=False, bias=None, res_before_act=False, out_len=None, shuffle=0, res_mul=False, plan_w=None):
     """y = [y +] out_scale * (act(conv(pre_act(x)) + bias) + res).  x: (N,C,T) or (N,C,H,W), last dim contiguous;
-    views with arbitrary batch/channel/row strides are accepted for x, res and out."""
+    views with arbitrary batch/channel/row strides are accepted for x, res and out.
+    `plan_w`: x is a window of a row of plan_w columns (the windowed vocoder) -- every size gate here and every tile policy of the
+    library counts with plan_w (aicg_conv_forward_planned), so that the window runs the kernel and tile of the uncropped layer."""
     is1d = x.dim() == 3
     x4 = _as4d(x)
     n, c, h, w = x4.shape
@@ -435,6 +437,8 @@ def conv(x, pc, res=None, out=None, pre_act=ACT_NONE, pre_slope=0.0, act=ACT_NON
     assert x4.stride(3) == 1 or w == 1
     # the kernels' range-checked buffer loads bound a channel chunk by its channel stride: a channel's rows must lie inside it
     assert h == 1 or c == 1 or x4.stride(1) >= x4.stride(2) * (h - 1) + w, "conv: input rows must lie inside the channel stride"
+    assert plan_w is None or plan_w >= w
+    gate_w = w if plan_w is None else int(plan_w)
     ho, wo = pc.out_hw(h, w)
     if out_len is not None:  # compute only the first out_len columns (e.g. SamePad of an even kernel)
         assert out_len <= wo
@@ -484,7 +488,7 @@ def conv(x, pc, res=None, out=None, pre_act=ACT_NONE, pre_slope=0.0, act=ACT_NON
     # the one-dimensional form F(2, 3) of a k = 3 / 7 / 11 layer (csrc/conv_g1w.h): aligned rows of a multiple of four positions
     # (layers of fewer than 16 output channels -- the vocoder's conv_post, 32 -> 1 -- are one HBM pass: the streaming kernels keep them)
     wino1 = (winograd1d and getattr(pc, "w_wino1", None) is not None and pc.cout >= 16 and is1d and not shuffle and out_len is None and w % 4 == 0
-             and n * w >= winograd1d_min_positions and pre_act in (ACT_NONE, ACT_LRELU) and 0.0 <= pre_slope <= 1.0
+             and n * gate_w >= winograd1d_min_positions and pre_act in (ACT_NONE, ACT_LRELU) and 0.0 <= pre_slope <= 1.0
              and not res_mul and w < (1 << 24) and x4.stride(1) < (1 << 24)      # what csrc/conv_g1w.h's conv_g1w_applicable() also demands
              and 15 * (-(-(c // pc.groups) // 32) * 32) * (-(-pc.cout // 32) * 32) * 4 < (1 << 31)
              and x4.data_ptr() % 16 == 0 and x4.stride(0) % 4 == 0 and x4.stride(1) % 4 == 0 and x4.stride(1) >= w
@@ -498,7 +502,11 @@ def conv(x, pc, res=None, out=None, pre_act=ACT_NONE, pre_slope=0.0, act=ACT_NON
     if prof is not None and x.is_cuda:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-    _call("aicg_conv_forward", ctypes.addressof(d), _ptr(x4), _ptr(pc.wino2_image(w2kind) if wino2 else pc.w_wino if wino else pc.w_wino1 if wino1 else pc.w), _ptr(b), _ptr(r4), _ptr(o4), _stream(x))
+    w_image = pc.wino2_image(w2kind) if wino2 else pc.w_wino if wino else pc.w_wino1 if wino1 else pc.w
+    if plan_w is None:
+        _call("aicg_conv_forward", ctypes.addressof(d), _ptr(x4), _ptr(w_image), _ptr(b), _ptr(r4), _ptr(o4), _stream(x))
+    else:
+        _call("aicg_conv_forward_planned", ctypes.addressof(d), _ptr(x4), _ptr(w_image), _ptr(b), _ptr(r4), _ptr(o4), gate_w, _stream(x))
     if prof is not None and x.is_cuda:
         e1.record()
         prof.events.append((e0, e1))
@@ -547,8 +555,9 @@ class PackedConvTranspose:
         return ho, wo
 
 
-def conv_transpose(x, pt, out=None, add=None, pre_act=ACT_NONE, pre_slope=0.0, act=ACT_NONE, act_slope=0.0, mul=None):
-    """y = act(conv_transpose(pre_act(x)) + bias) + add   (or ... * mul: the MDX U-Net's multiplicative skip)."""
+def conv_transpose(x, pt, out=None, add=None, pre_act=ACT_NONE, pre_slope=0.0, act=ACT_NONE, act_slope=0.0, mul=None, plan_w=None):
+    """y = act(conv_transpose(pre_act(x)) + bias) + add   (or ... * mul: the MDX U-Net's multiplicative skip).
+    `plan_w`: as in conv() -- the row length x was cut from (1-D layers)."""
     is1d = x.dim() == 3
     x4 = _as4d(x)
     n, c, h, w = x4.shape
@@ -558,7 +567,7 @@ def conv_transpose(x, pt, out=None, add=None, pre_act=ACT_NONE, pre_slope=0.0, a
         # non-overlapping taps: every output element is one GEMM element -> scatter + bias + act + skip in the GEMM epilogue
         return conv(x4, pt.gemm, res=add if mul is None else mul, out=out, pre_act=pre_act, pre_slope=pre_slope, act=act,
                     act_slope=act_slope, bias=pt.bias4, shuffle=2, res_mul=mul is not None)
-    cols = conv(x4, pt.gemm, pre_act=pre_act, pre_slope=pre_slope)  # (N, Cout*KH*KW, H, W)
+    cols = conv(x4, pt.gemm, pre_act=pre_act, pre_slope=pre_slope, plan_w=plan_w)  # (N, Cout*KH*KW, H, W)
     ho, wo = pt.out_hw(h, w)
     if out is None:
         out = torch.empty((n, pt.cout, wo) if is1d else (n, pt.cout, ho, wo), dtype=torch.float32, device=x.device)
@@ -592,6 +601,26 @@ def sine_source(f0, noise, upp, sr, lin_w, lin_b, sine_amp=0.1, noise_std=0.003)
     _call("aicg_sine_source", _ptr(f0), _ptr(noise), _ptr(prefix), _ptr(out), t, int(upp), float(sr), sine_amp,
               noise_std, float(lin_w), float(lin_b), _stream(f0))
     return out
+
+
+def sine_source_window(f0, noise, upp, sr, lin_w, lin_b, first, count, sine_amp=0.1, noise_std=0.003):
+    """Samples first .. first + count - 1 of sine_source(f0, noise, ...) -- the same bits: the phase is integrated from frame 0 and sample
+    n reads noise[n] of the full-length draw --, zero where that index lies outside the signal (first may be negative: the zero
+    padding of the vocoder's noise convolutions).  Only the window is written."""
+    f0 = f0.contiguous().float()
+    noise = noise.contiguous().float()
+    t = f0.numel()
+    first, count = int(first), int(count)
+    assert noise.numel() == t * upp and count >= 0
+    _check(f0, noise)
+    # the library cuts a source it generates in quads (upp % 4 == 0) on quads: ask for the enclosing quads, return the slice
+    lead = first % 4 if upp % 4 == 0 else 0
+    n = -(-(lead + count) // 4) * 4 if upp % 4 == 0 else count
+    prefix = torch.empty(max(t, 1), dtype=torch.float64, device=f0.device)
+    out = torch.empty(n, dtype=torch.float32, device=f0.device)
+    _call("aicg_sine_source_window", _ptr(f0), _ptr(noise), _ptr(prefix), _ptr(out), t, int(upp), float(sr), sine_amp,
+              noise_std, float(lin_w), float(lin_b), first - lead, n, _stream(f0))
+    return out[lead: lead + count]
 
 
 def gate_tanh_sigmoid(a, out=None):
@@ -1434,5 +1463,6 @@ dense_nt = _staged("dense_gemm_nt", dense_nt, _gemm_work)
 attention = _staged("attention", attention, lambda a, k, r: (4.0 * a[0].numel() * a[0].shape[1],      # 4 T^2 D per head
                                                              4.0 * _numel(a[0], a[1], a[2], r)))
 sine_source = _staged("sine_source", sine_source, lambda a, k, r: (0.0, 4.0 * _numel(a[0], a[1], r)))
+sine_source_window = _staged("sine_source", sine_source_window, lambda a, k, r: (0.0, 4.0 * _numel(a[0], r, r)))
 layernorm_ct = _staged("layernorm", layernorm_ct, lambda a, k, r: (0.0, 4.0 * _numel(a[0], k.get("res"), r)))
 rownorm_act = _staged("groupnorm_gelu", rownorm_act, lambda a, k, r: (0.0, 4.0 * _numel(a[0], r)))

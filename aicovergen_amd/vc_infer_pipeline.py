@@ -317,17 +317,19 @@ class VC(object):
 
     # ---- one chunk ----------------------------------------------------------------------------------------------
     def vc(self, model, net_g, sid, audio0, pitch, pitchf, times, index, big_npy, index_rate, version, protect,
-           noise=None, keep_on_device=False):
+           noise=None, keep_on_device=False, trim=0):
         """One padded chunk -> float32 waveform at tgt_sr (reference :372-472).  `noise` = (noise_z, noise_src)
         replaces the synthesizer's random draws (parity tests); `keep_on_device` returns the waveform as a device
-        tensor instead of the reference's numpy array (used by pipeline(), which post-processes on the device)."""
+        tensor instead of the reference's numpy array (used by pipeline(), which post-processes on the device).
+        `trim`: return the waveform without its first and last `trim` samples (pipeline(): the chunk's padding) -- a synthesizer with
+        the front / back split then does not synthesise them either (_vc_synth_back)."""
         t0 = ttime()
         feats, feats0 = self._vc_features(model, audio0, index, big_npy, index_rate, version,
                                           protect < 0.5 and pitch is not None and pitchf is not None)
         if self._sync():
             torch.cuda.synchronize()
         t1 = ttime()
-        o = self._vc_synth(net_g, sid, audio0.shape[0], feats, feats0, pitch, pitchf, protect, noise)
+        o = self._vc_synth(net_g, sid, audio0.shape[0], feats, feats0, pitch, pitchf, protect, noise, trim)
         if keep_on_device:
             if self._sync():
                 torch.cuda.synchronize()
@@ -379,15 +381,23 @@ class VC(object):
             feats = torch.from_numpy(npy.astype("float32")).unsqueeze(0).to(self.device) * index_rate + (1 - index_rate) * feats
         return feats, feats0
 
-    def _vc_synth(self, net_g, sid, n_samples, feats, feats0, pitch, pitchf, protect, noise):
+    def _vc_synth(self, net_g, sid, n_samples, feats, feats0, pitch, pitchf, protect, noise, trim=0):
         """Features (+ pitch) of one chunk -> synthesizer output (1, 1, T) on the device, reference :433-466."""
-        return self._vc_synth_back(net_g, self._vc_synth_front(net_g, sid, n_samples, feats, feats0, pitch, pitchf, protect, noise))
+        return self._vc_synth_back(net_g, self._vc_synth_front(net_g, sid, n_samples, feats, feats0, pitch, pitchf, protect, noise), trim)
 
-    def _vc_synth_back(self, net_g, st):
-        """Vocoder half of a chunk's synthesis (state from _vc_synth_front)."""
+    def _vc_synth_back(self, net_g, st, trim=0):
+        """Vocoder half of a chunk's synthesis (state from _vc_synth_front), without the first and last `trim` samples (the reference
+        synthesises the whole padded chunk and slices, :567-649).  The vocoder is convolutional: the kept samples depend on a few frames
+        of the padding only (net_g.decoder_reach()), so infer_back is told the kept range and skips the rest of it -- the same samples,
+        bit for bit (tests/test_synth_window.py).  AICG_SYNTH_WINDOW=0 (development switch): synthesise everything, then slice."""
         if "front" not in st:
-            return st["o"]
-        return net_g.infer_back(st["front"], st["pitchf"], st["ns"])[0]
+            o = st["o"]
+        else:
+            n = st["front"]["z"].shape[2] * net_g.upp
+            if trim and n > 2 * trim and _env.dev("AICG_SYNTH_WINDOW", "1") != "0":
+                return net_g.infer_back(st["front"], st["pitchf"], st["ns"], keep=(trim, n - trim))[0]
+            o = net_g.infer_back(st["front"], st["pitchf"], st["ns"])[0]
+        return o[:, :, trim: o.shape[2] - trim] if trim else o
 
     def _vc_synth_front(self, net_g, sid, n_samples, feats, feats0, pitch, pitchf, protect, noise):
         """Encoder half of a chunk's synthesis: nearest x2 upsample + protect blend, text encoder, prior sample, reverse flow.
@@ -646,23 +656,23 @@ class VC(object):
         pc, pcf = c.chunk_pitch(ci)
         if not c.overlap:       # serial: vc() runs features and synthesis and accumulates times[0] / times[2] itself
             out = self.vc(c.model, c.net_g, c.sid, c.audio_pad[s:e], pc, pcf, c.times, c.index, c.big_npy, c.index_rate, c.version,
-                          c.protect, noise=c.noise(ci), keep_on_device=True)
+                          c.protect, noise=c.noise(ci), keep_on_device=True, trim=self.t_pad_tgt)
         else:
             noise = c.noise(ci) if front is None else None
             ts0 = ttime()
             if front is not None:
                 st, ev, keep = front    # the front's inputs stay referenced until the drain below: nothing is recycled under the other stream
                 c.main.wait_event(ev)
-                out = self._vc_synth_back(c.net_g, st)[0, 0]
+                out = self._vc_synth_back(c.net_g, st, self.t_pad_tgt)[0, 0]
                 if after is not None:
                     self._queue_front(c, after)
             else:
                 feats, feats0 = c.feats_of.pop(ci)
                 c.wait_pitch(c.main, ci)
-                out = self._vc_synth(c.net_g, c.sid, e - s, feats, feats0, pc, pcf, c.protect, noise)[0, 0]
+                out = self._vc_synth(c.net_g, c.sid, e - s, feats, feats0, pc, pcf, c.protect, noise, self.t_pad_tgt)[0, 0]
             c.drain()
             c.times[2] += ttime() - ts0
-        c.pieces[ci] = out[self.t_pad_tgt: -self.t_pad_tgt]
+        c.pieces[ci] = out      # already without the chunk's padding (_vc_synth_back)
         return c.pieces[ci]
 
     def _chunk_loop(self, c):

@@ -158,6 +158,12 @@ int aicg_conv_bkc(int taps);
 int aicg_conv_desc_size(void);
 int aicg_conv_forward(const aicg_conv_desc* desc, const float* x, const float* w_packed, const float* bias,
                       const float* res, float* y, void* stream);
+/* The same layer on a CROPPED map: desc describes the W columns that are computed, plan_w (>= desc->W, or 0 = desc->W) the row length of
+ * the uncropped problem the columns were cut from.  Every routing decision that counts output positions or workgroups -- which kernel
+ * family fills the chip, which tile -- is taken for plan_w columns, so that a cropped launch runs the kernel and tile of the uncropped
+ * one (the windowed vocoder: its kept samples keep their summation order).  Alignment demands are still those of the real map. */
+int aicg_conv_forward_planned(const aicg_conv_desc* desc, const float* x, const float* w_packed, const float* bias,
+                              const float* res, float* y, int plan_w, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Transposed convolution, second half: cols = (Cout*KH*KW, Cin) x input computed by aicg_conv_forward as a
@@ -177,6 +183,14 @@ int aicg_col2im(const float* cols, const float* bias, const float* add, float* o
  * prefix_scratch: [T] doubles; out: [T*upp] = tanh(lin_w * (sine*uv + noise_amp*noise) + lin_b). */
 int aicg_sine_source(const float* f0, const float* noise, double* prefix_scratch, float* out, int T, int upp,
                      float sr, float sine_amp, float noise_std, float lin_w, float lin_b, void* stream);
+/* A WINDOW of that source: out[j] = the sample first + j of the T * upp samples aicg_sine_source writes, j = 0 .. count - 1, and zero
+ * where first + j lies outside [0, T * upp) (the zero padding of the noise convolutions).  The phase is still integrated from frame 0
+ * and sample n still consumes noise[n] (the full-length draw): every sample has the bits of the full call.  first may be negative;
+ * where upp % 4 == 0 (the full call works in quads) first and count must be multiples of 4, so that the window is cut on the same quads;
+ * prefix_scratch: [T] doubles (frames behind the window are not scanned). */
+int aicg_sine_source_window(const float* f0, const float* noise, double* prefix_scratch, float* out, int T, int upp,
+                            float sr, float sine_amp, float noise_std, float lin_w, float lin_b, int64_t first, int64_t count,
+                            void* stream);
 
 /* commons.fused_add_tanh_sigmoid_multiply (src/infer_pack/commons.py:105-112); the conditioning slice is a
  * per-channel constant for a (1,C,1) speaker embedding and is folded into the producing conv's bias.

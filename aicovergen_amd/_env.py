@@ -11,7 +11,7 @@ Supported in a user's process:
                                  libraries.  Unset, run_main.py leaves those imports to whatever is installed
 
 Everything else -- kernel-form selectors (AICG_WINOGRAD, AICG_WINOGRAD1D, AICG_W2D_*, AICG_GRU_*), schedule selectors (AICG_F0_SEGMENTS,
-AICG_OVERLAP_F0, AICG_OVERLAP_SYNTH, AICG_F0_PRIORITY, AICG_RB_STREAMS, AICG_MDX_BATCH) and reference-path selectors (AICG_FILTFILT,
+AICG_OVERLAP_F0, AICG_OVERLAP_SYNTH, AICG_F0_PRIORITY, AICG_RB_STREAMS, AICG_MDX_BATCH, AICG_SONG_CACHE) and reference-path selectors (AICG_FILTFILT,
 AICG_GPU_KNN, AICG_KNN) -- changes routing or summation ORDER (never the arithmetic's meaning) and exists for A/B measurements and for
 the tests that pin one form against another.  They are DEVELOPMENT switches: read through dev() and honoured only when AICG_DEV=1 is
 set too, so that a stray variable in a user's shell cannot silently change which kernels run.  tests/conftest.py

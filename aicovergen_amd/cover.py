@@ -29,7 +29,7 @@ import wave
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _env, _lib, ops
 
 _LN2_30 = 30.0 * math.log(2.0)
 
@@ -421,6 +421,30 @@ class _Fetch:
             writer(path, host.numpy(), *args)
         self.jobs = []
 
+    def paths(self):
+        return [job[1] for job in self.jobs]
+
+    def flush_in_background(self):
+        """Write the files from a thread of its own (waiting for a copy, writing a file and waiting for ffmpeg all release the GIL) while
+        the caller queues the next cover; join() re-raises what went wrong there."""
+        import threading
+        self.error = None
+
+        def work():
+            try:
+                self.flush()
+            except BaseException as e:      # handed to the thread that joins
+                self.error = e
+        self.thread = threading.Thread(target=work, name="aicg-cover-files")
+        self.thread.start()
+
+    def join(self):
+        t, self.thread = getattr(self, "thread", None), None
+        if t is not None:
+            t.join()
+            if self.error is not None:
+                raise self.error
+
 
 def _write_wavfile(path, pcm, sr):      # what run_mdx (soundfile's PCM-16) and rvc_infer leave: scipy's writer on int16 samples
     from scipy.io import wavfile
@@ -430,6 +454,31 @@ def _write_wavfile(path, pcm, sr):      # what run_mdx (soundfile's PCM-16) and 
 def _planar(pcm):
     """(frames, C) int16 PCM -> (C, frames) float32 / 32768: what read_float makes of the stem's file."""
     return pcm.t().contiguous().to(torch.float32) / 32768.0
+
+
+class _Song:
+    """What a session keeps of the last song, all of it independent of the voice: the three int16 stems the mix and the conversion need
+    (device tensors, as _separate leaves them or as their files read), the 16 kHz mono hand-over of the de-reverbed stem, the backing
+    stems shifted by `pitch_change_all` (per value seen) and the VoiceFronts (per f0 method / hop / filter radius / if_f0 / version).
+    `stamp`: size and mtime of the three stem files when they were cached -- main.py's rules look at the files, so stems somebody
+    replaced on disk are read again."""
+
+    def __init__(self, song_id, paths, inst, inst_sr, backup, backup_sr, dereverb):
+        self.id, self.paths = song_id, paths
+        self.inst, self.inst_sr, self.backup, self.backup_sr, self.dereverb = inst, inst_sr, backup, backup_sr, dereverb
+        self.audio16k, self.shifted, self.fronts, self.stamp = None, {}, {}, None
+
+    @staticmethod
+    def stamp_of(paths):
+        try:
+            return tuple((os.path.getsize(p), os.stat(p).st_mtime_ns) for p in paths[1:])
+        except OSError:
+            return None
+
+    def nbytes(self):
+        ts = [self.inst, self.backup, self.dereverb] + ([self.audio16k] if self.audio16k is not None else [])
+        ts += [t for pair in self.shifted.values() for t in pair]
+        return sum(t.numel() * t.element_size() for t in ts) + sum(f.nbytes() for f in self.fronts.values())
 
 
 class CoverSession:
@@ -449,6 +498,15 @@ class CoverSession:
         self.voices = {}                                                 # directory name -> (cpt, version, net_g, tgt_sr, vc, index path)
         self.profile_stages = False      # True: drain the device after every stage and keep the wall-clock split in last_profile
         self.last_profile = {}
+        self.song = None                 # the last song's voice-independent part (_Song); capacity: one song
+
+    def drop_song(self):
+        """Forget the cached song: its stems, hand-over, shifted stems and fronts leave device memory."""
+        self.song = None
+
+    @staticmethod
+    def _song_cache_on():
+        return _env.dev("AICG_SONG_CACHE", "1") != "0"      # development switch: "0" = every call starts from the files, as before the cache
 
     def voice(self, voice_model):
         from . import rvc
@@ -494,14 +552,26 @@ class CoverSession:
         return song_path, path("Instrumental"), path("Vocals_Main_DeReverb"), path("Vocals_Backup"), inst, backup, dereverb
 
     def _convert(self, voice_model, dereverb, dereverb_path, pitch_change, f0_method, index_rate, filter_radius, rms_mix_rate, protect,
-                 crepe_hop_length, noise_seed):
+                 crepe_hop_length, noise_seed, song=None):
         """main.py's voice_change (:193-203) without the file on either side: the de-reverbed stem -> 16 kHz mono on the device
-        (ops.resample_poly_mono, bench.py's hand-over) -> VC.pipeline -> (int16 (n,) device tensor, its rate)."""
+        (ops.resample_poly_mono, bench.py's hand-over) -> VC.pipeline -> (int16 (n,) device tensor, its rate).
+        `song` (the session's cache entry): the hand-over and the voice-independent front of the conversion (VC.front: plan, f0
+        estimate, HuBERT) are taken from it, or made once and left there; the samples are the same (tests/test_voice_front.py)."""
         cpt, version, net_g, tgt_sr, vc, index_path = self.voice(voice_model)
-        audio = ops.resample_poly_mono(_planar(dereverb), 44100, 16000)
+        if_f0, front = cpt.get("f0", 1), None
+        if song is None:
+            audio = ops.resample_poly_mono(_planar(dereverb), 44100, 16000)
+        else:
+            if song.audio16k is None:
+                song.audio16k = ops.resample_poly_mono(_planar(dereverb), 44100, 16000)
+            audio = song.audio16k
+            key = (f0_method, crepe_hop_length, filter_radius, if_f0, version)
+            if key not in song.fronts:
+                song.fronts[key] = vc.front(self.hubert, audio, dereverb_path, f0_method, if_f0, version, filter_radius, crepe_hop_length)
+            front = song.fronts[key]
         out = vc.pipeline(self.hubert, net_g, 0, audio, dereverb_path, [0, 0, 0], pitch_change, f0_method, index_path, index_rate,
-                          cpt.get("f0", 1), filter_radius, tgt_sr, 0, rms_mix_rate, version, protect, crepe_hop_length,
-                          noise_seed=noise_seed, device_out=True)
+                          if_f0, filter_radius, tgt_sr, 0, rms_mix_rate, version, protect, crepe_hop_length,
+                          noise_seed=noise_seed, device_out=True, front=front)
         return out, tgt_sr
 
     def song_cover_pipeline(self, song_input, voice_model, pitch_change, keep_files, is_webui=0, main_gain=0, backup_gain=0,
@@ -511,8 +581,21 @@ class CoverSession:
         """main.py's song_cover_pipeline (src/main.py:236-313) with its parameters, defaults, file names and return value (the
         cover's path); `is_webui` and `progress` are accepted and ignored, `noise_seed` seeds the synthesizer's noise per chunk
         (VC.pipeline).  Every stem stays in device memory from the song file to the cover; only the files main.py leaves behind
-        are copied to the host (all of them with keep_files)."""
-        import time
+        are copied to the host (all of them with keep_files).
+        The same song again -- another voice, another `-p` -- finds its voice-independent part in the session (_Song): the stems are
+        not read and uploaded again, nor resampled, nor passed through the f0 estimator and HuBERT, nor shifted by `-pall` a second
+        time.  main.py's file rules come first: keep_files separates again, missing or replaced stem files are made or read again, an
+        existing AI-vocals or `_p{N}.wav` file is used as it is.  The files and their bytes are those of a call on a fresh session."""
+        path, fetch = self._cover(song_input, voice_model, pitch_change, keep_files, main_gain, backup_gain, inst_gain, index_rate,
+                                  filter_radius, rms_mix_rate, f0_method, crepe_hop_length, protect, pitch_change_all, reverb_rm_size,
+                                  reverb_wet, reverb_dry, reverb_damping, output_format, noise_seed)
+        t0 = __import__("time").perf_counter()
+        fetch.flush()
+        self._mark("files_s", t0)
+        return path
+
+    @staticmethod
+    def _checked_input(song_input, voice_model):
         from urllib.parse import urlparse
         if not song_input or not voice_model:
             raise ValueError("Ensure that the song input field and voice model field is filled.")
@@ -521,6 +604,48 @@ class CoverSession:
         song_input = song_input.strip('"')
         if not os.path.exists(song_input):
             raise FileNotFoundError(f"{song_input} does not exist.")
+        return song_input
+
+    def _stems(self, song_input, song_id, song_dir, keep_files, fetch, dev):
+        """The song's stems and their paths (main.py:252-266) -> (paths, inst, inst_sr, backup, backup_sr, dereverb, cache entry or None,
+        whether `fetch` now holds stem files)."""
+        cached = None
+        if os.path.exists(song_dir):
+            paths = get_audio_paths(song_dir)
+            if not (any(p is None for p in paths) or keep_files):
+                cached = paths
+        else:
+            os.makedirs(song_dir)
+        cache = self._song_cache_on()
+        if not cache or (self.song is not None and self.song.id != song_id):
+            self.song = None                                                        # capacity: one song
+        if cached is not None and self.song is not None and (self.song.paths[1:] != tuple(cached[1:])
+                                                             or self.song.stamp != _Song.stamp_of(cached)):
+            self.song = None                                                        # the files are not the ones that were cached
+        if cached is not None and self.song is not None:
+            g = self.song
+            return cached, g.inst, g.inst_sr, g.backup, g.backup_sr, g.dereverb, g, False
+        if cached is None:
+            orig_song_path, inst_path, dereverb_path, backup_path, inst, backup, dereverb = self._separate(song_input, song_dir,
+                                                                                                          keep_files, fetch)
+            inst_sr = backup_sr = 44100
+            paths = (orig_song_path, inst_path, dereverb_path, backup_path)
+        else:
+            paths = orig_song_path, inst_path, dereverb_path, backup_path = cached
+            (inst, inst_sr), (backup, backup_sr), (dereverb, _) = [
+                (torch.from_numpy(np.ascontiguousarray(d)).to(dev), sr) for d, sr in map(read_pcm16, (inst_path, backup_path, dereverb_path))]
+        self.song = _Song(song_id, tuple(paths), inst, inst_sr, backup, backup_sr, dereverb) if cache else None
+        if self.song is not None and cached is not None:
+            self.song.stamp = _Song.stamp_of(paths)
+        return paths, inst, inst_sr, backup, backup_sr, dereverb, self.song, cached is None
+
+    def _cover(self, song_input, voice_model, pitch_change, keep_files, main_gain, backup_gain, inst_gain, index_rate, filter_radius,
+               rms_mix_rate, f0_method, crepe_hop_length, protect, pitch_change_all, reverb_rm_size, reverb_wet, reverb_dry,
+               reverb_damping, output_format, noise_seed, before_convert=None):
+        """song_cover_pipeline up to the files: everything is queued, the _Fetch that will write them is returned with the cover's path.
+        `before_convert(ai_vocals_path)`: called before the file checks of the per-voice part (song_covers joins its writer there)."""
+        import time
+        song_input = self._checked_input(song_input, voice_model)
         song_id = get_hash(song_input)
         song_dir = os.path.join(self.output_dir, song_id)
         on_gpu = _lib.backend() == "hip"
@@ -529,21 +654,8 @@ class CoverSession:
         self.last_profile = {}
         t0 = time.perf_counter()
 
-        cached = None
-        if os.path.exists(song_dir):
-            paths = get_audio_paths(song_dir)
-            if not (any(p is None for p in paths) or keep_files):
-                cached = paths
-        else:
-            os.makedirs(song_dir)
-        if cached is None:
-            orig_song_path, inst_path, dereverb_path, backup_path, inst, backup, dereverb = self._separate(song_input, song_dir,
-                                                                                                          keep_files, fetch)
-            inst_sr = backup_sr = 44100
-        else:
-            orig_song_path, inst_path, dereverb_path, backup_path = cached
-            (inst, inst_sr), (backup, backup_sr), (dereverb, _) = [
-                (torch.from_numpy(np.ascontiguousarray(d)).to(dev), sr) for d, sr in map(read_pcm16, (inst_path, backup_path, dereverb_path))]
+        (orig_song_path, inst_path, dereverb_path, backup_path), inst, inst_sr, backup, backup_sr, dereverb, song, fetch.has_stems = \
+            self._stems(song_input, song_id, song_dir, keep_files, fetch, dev)
         t0 = self._mark("separate_s", t0)
 
         pitch_change = pitch_change * 12 + pitch_change_all
@@ -552,34 +664,39 @@ class CoverSession:
         ai_vocals_path = os.path.join(song_dir, f"{base}_{voice_model}_p{pitch_change}_i{index_rate}_fr{filter_radius}_rms{rms_mix_rate}"
                                                 f"_pro{protect}_{f0_method}{hop}.wav")
         ai_cover_path = os.path.join(song_dir, f"{base} ({voice_model} Ver).{output_format}")
+        if before_convert is not None:
+            before_convert(ai_vocals_path)
 
         # the backing stems' pitch shift does not depend on the conversion: one persistent workgroup per stem, queued on a side stream
         # before the conversion starts and joined before the mix
-        shifted = {}
+        shifted, side, from_file = {}, None, False
         if pitch_change_all != 0:
+            kept = song.shifted.get(pitch_change_all) if song is not None else None
             main_stream = torch.cuda.current_stream() if on_gpu else _NoStream()
             side = torch.cuda.Stream() if on_gpu else _NoStream()
             side.wait_stream(main_stream)
             with (torch.cuda.stream(side) if on_gpu else side):
-                for key, pcm, sr, src in (("inst", inst, inst_sr, inst_path), ("backup", backup, backup_sr, backup_path)):
+                for k, (key, pcm, sr, src) in enumerate((("inst", inst, inst_sr, inst_path), ("backup", backup, backup_sr, backup_path))):
                     out_path = f"{os.path.splitext(src)[0]}_p{pitch_change_all}.wav"
                     if os.path.exists(out_path):                                    # main.py:140: an existing file is used as it is
-                        y = torch.from_numpy(np.ascontiguousarray(read_pcm16(out_path)[0])).to(dev)
+                        y, from_file = torch.from_numpy(np.ascontiguousarray(read_pcm16(out_path)[0])).to(dev), True
                     else:
-                        y = ops.fx_to_pcm16(pitch_shift_signal(_planar(pcm), sr, pitch_change_all)[0])
+                        y = kept[k] if kept is not None else ops.fx_to_pcm16(pitch_shift_signal(_planar(pcm), sr, pitch_change_all)[0])
                         if keep_files:
                             fetch.add(write_pcm16, out_path, y, sr)
                     if on_gpu:
                         pcm.record_stream(side)
                         y.record_stream(main_stream)
                     shifted[key] = y
+            if song is not None and kept is None and not from_file:
+                song.shifted[pitch_change_all] = (shifted["inst"], shifted["backup"])
 
         if os.path.exists(ai_vocals_path):                                          # main.py:289
             ai, ai_sr = read_pcm16(ai_vocals_path)
             ai = torch.from_numpy(np.ascontiguousarray(ai)).to(dev)
         else:
             ai, ai_sr = self._convert(voice_model, dereverb, dereverb_path, pitch_change, f0_method, index_rate, filter_radius,
-                                      rms_mix_rate, protect, crepe_hop_length, noise_seed)
+                                      rms_mix_rate, protect, crepe_hop_length, noise_seed, song)
             fetch.add(_write_wavfile, ai_vocals_path, ai, ai_sr)
             ai = ai.view(-1, 1)
         t0 = self._mark("convert_s", t0)
@@ -595,10 +712,71 @@ class CoverSession:
             inst, backup = shifted["inst"], shifted["backup"]
         out, sr = mix_stems(mixed, ai_sr, backup, backup_sr, inst, inst_sr, main_gain, backup_gain, inst_gain)
         fetch.add(lambda p, pcm, r: export(pcm, r, p, output_format), ai_cover_path, out, sr)
-        t0 = self._mark("pitch_join_and_mix_s", t0)
-        fetch.flush()
-        self._mark("files_s", t0)
-        return ai_cover_path
+        self._mark("pitch_join_and_mix_s", t0)
+        if song is not None and fetch.has_stems:      # stems that this call writes: stamped once their files exist
+            flush = fetch.flush
+
+            def flush_and_stamp():
+                flush()
+                song.stamp = _Song.stamp_of(song.paths)
+            fetch.flush = flush_and_stamp
+        return ai_cover_path, fetch
+
+    PER_COVER = ("pitch_change", "main_gain", "backup_gain", "inst_gain", "index_rate", "filter_radius", "rms_mix_rate", "f0_method",
+                 "crepe_hop_length", "protect", "pitch_change_all", "reverb_rm_size", "reverb_wet", "reverb_dry", "reverb_damping",
+                 "output_format", "noise_seed")
+    DEFAULTS = dict(main_gain=0, backup_gain=0, inst_gain=0, index_rate=0.5, filter_radius=3, rms_mix_rate=0.25, f0_method="rmvpe",
+                    crepe_hop_length=128, protect=0.33, pitch_change_all=0, reverb_rm_size=0.15, reverb_wet=0.2, reverb_dry=0.8,
+                    reverb_damping=0.7, output_format="mp3", noise_seed=None)
+
+    def song_covers(self, song_input, voices, keep_files=False, **common):
+        """One song, several covers: `voices` is a list of dicts with `voice_model` and any of song_cover_pipeline's per-cover parameters
+        (PER_COVER), `common` their defaults for all entries -> the cover paths in order.  The same files, byte for byte, as one
+        song_cover_pipeline call per entry; the separation, the front of the conversion and the `-pall` shift are queued once (per f0
+        method / `pitch_change_all` where the entries differ), and the files of cover k are written by a thread of their own while
+        cover k + 1 is on the device.  Two entries that would write the same cover file raise ValueError before any work (main.py, run
+        twice, silently overwrites the first)."""
+        unknown = sorted(set(common) - set(self.PER_COVER))
+        if unknown:
+            raise TypeError("song_covers: unknown parameter(s) %s" % ", ".join(unknown))
+        entries, seen = [], {}
+        for k, v in enumerate(voices):
+            unknown = sorted(set(v) - set(self.PER_COVER) - {"voice_model"})
+            if unknown or not v.get("voice_model"):
+                raise ValueError("song_covers: entry %d needs a voice_model and takes only per-cover parameters (%s)" % (k, ", ".join(unknown)))
+            e = dict(self.DEFAULTS, **common)
+            e.update(v)
+            if "pitch_change" not in e:
+                raise ValueError("song_covers: entry %d (%s) has no pitch_change" % (k, e["voice_model"]))
+            name = (e["voice_model"], e["output_format"])         # what the cover's file name is made of (main.py:287)
+            if name in seen:
+                raise ValueError("song_covers: entries %d and %d would both write '... (%s Ver).%s'" % (seen[name], k, *name))
+            seen[name] = k
+            entries.append(e)
+        self._checked_input(song_input, entries[0]["voice_model"] if entries else "-")
+        covers, writer = [], None
+        try:
+            for e in entries:
+                pending = writer.paths() if writer is not None else []
+
+                def before_convert(ai_vocals_path, _w=writer, _p=pending):
+                    if _w is not None and (keep_files or ai_vocals_path in _p):      # a file this cover looks for may be on its way
+                        _w.join()
+                args = [e[k] for k in self.PER_COVER]
+                path, fetch = self._cover(song_input, e["voice_model"], args[0], keep_files, *args[1:], before_convert=before_convert)
+                if writer is not None:
+                    writer.join()
+                if fetch.has_stems:       # the next entry finds the song by its stem files (main.py:252-262): they are written now
+                    fetch.flush()
+                    writer = None
+                else:
+                    fetch.flush_in_background()
+                    writer = fetch
+                covers.append(path)
+        finally:
+            if writer is not None:
+                writer.join()
+        return covers
 
 
 _default_session = None
@@ -621,12 +799,20 @@ def song_cover_pipeline(song_input, voice_model, pitch_change, keep_files, **kwa
     return default_session().song_cover_pipeline(song_input, voice_model, pitch_change, keep_files, **kwargs)
 
 
+class _OneOrMore(__import__("argparse").Action):
+    """`-dir A`: the string "A", as main.py parses it; `-dir A -dir B`: the list ["A", "B"]."""
+
+    def __call__(self, parser, namespace, value, option_string=None):
+        have = getattr(namespace, self.dest, None)
+        setattr(namespace, self.dest, value if have is None else (have if isinstance(have, list) else [have]) + [value])
+
+
 def build_parser():
     """main.py's command line (src/main.py:320-339: same flags, same defaults) plus the three directories."""
     import argparse
     p = argparse.ArgumentParser(description="Generate a AI cover song in the song_output/id directory.", add_help=True)
     p.add_argument("-i", "--song-input", type=str, required=True, help="Filepath to a local audio file to create an AI cover of")
-    p.add_argument("-dir", "--rvc-dirname", type=str, required=True, help="Name of the folder in the rvc_models directory containing the RVC model file and optional index file to use")
+    p.add_argument("-dir", "--rvc-dirname", type=str, required=True, action=_OneOrMore, help="Name of the folder in the rvc_models directory containing the RVC model file and optional index file to use (repeat the flag for several covers of the song)")
     p.add_argument("-p", "--pitch-change", type=int, required=True, help="Change the pitch of AI Vocals only. Generally, use 1 for male to female and -1 for vice-versa. (Octaves)")
     p.add_argument("-k", "--keep-files", action=argparse.BooleanOptionalAction, help="Whether to keep all intermediate audio files generated in the song_output/id directory")
     p.add_argument("-ir", "--index-rate", type=float, default=0.5, help="How much of the retrieved features to mix in (0 to 1)")
@@ -652,17 +838,25 @@ def build_parser():
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    if not os.path.exists(os.path.join(args.rvc_models_dir, args.rvc_dirname)):
-        raise Exception(f"The folder {os.path.join(args.rvc_models_dir, args.rvc_dirname)} does not exist.")
+    dirnames = args.rvc_dirname if isinstance(args.rvc_dirname, list) else [args.rvc_dirname]
+    for name in dirnames:
+        if not os.path.exists(os.path.join(args.rvc_models_dir, name)):
+            raise Exception(f"The folder {os.path.join(args.rvc_models_dir, name)} does not exist.")
     session = CoverSession(args.mdx_models_dir, args.rvc_models_dir, args.output_dir)
-    cover_path = session.song_cover_pipeline(
-        args.song_input, args.rvc_dirname, args.pitch_change, args.keep_files, main_gain=args.main_vol, backup_gain=args.backup_vol,
-        inst_gain=args.inst_vol, index_rate=args.index_rate, filter_radius=args.filter_radius, rms_mix_rate=args.rms_mix_rate,
-        f0_method=args.pitch_detection_algo, crepe_hop_length=args.crepe_hop_length, protect=args.protect,
-        pitch_change_all=args.pitch_change_all, reverb_rm_size=args.reverb_size, reverb_wet=args.reverb_wetness,
-        reverb_dry=args.reverb_dryness, reverb_damping=args.reverb_damping, output_format=args.output_format)
-    print(f"[+] Cover generated at {cover_path}")
-    return cover_path
+    shared = dict(main_gain=args.main_vol, backup_gain=args.backup_vol,
+                  inst_gain=args.inst_vol, index_rate=args.index_rate, filter_radius=args.filter_radius, rms_mix_rate=args.rms_mix_rate,
+                  f0_method=args.pitch_detection_algo, crepe_hop_length=args.crepe_hop_length, protect=args.protect,
+                  pitch_change_all=args.pitch_change_all, reverb_rm_size=args.reverb_size, reverb_wet=args.reverb_wetness,
+                  reverb_dry=args.reverb_dryness, reverb_damping=args.reverb_damping, output_format=args.output_format)
+    if len(dirnames) == 1:
+        cover_path = session.song_cover_pipeline(args.song_input, dirnames[0], args.pitch_change, args.keep_files, **shared)
+        print(f"[+] Cover generated at {cover_path}")
+        return cover_path
+    cover_paths = session.song_covers(args.song_input, [{"voice_model": name} for name in dirnames], bool(args.keep_files),
+                                      pitch_change=args.pitch_change, **shared)
+    for cover_path in cover_paths:
+        print(f"[+] Cover generated at {cover_path}")
+    return cover_paths
 
 
 if __name__ == "__main__":

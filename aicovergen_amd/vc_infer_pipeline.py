@@ -86,7 +86,8 @@ def _bracket_pipeline(fn):
 class _Call:
     """One VC.pipeline call: the arguments its chunk routine needs (model, net_g, sid, index, big_npy, index_rate, version, protect, if_f0,
     noise_fn, times, f0_args = get_f0's positional arguments), the track (audio_pad, bounds, p_len, mine = this rank's chunks), the schedule
-    VC._schedule chose ("serial" | "one_launch" | "progressive", nseg, two_streams), and what the schedule's steps hand to each other."""
+    VC._schedule chose ("serial" | "one_launch" | "progressive", nseg, two_streams; "front" with `front` = the VoiceFront the call was
+    given), and what the schedule's steps hand to each other."""
 
     def __init__(self, **args):
         self.__dict__.update(args)
@@ -148,6 +149,31 @@ class _Call:
             torch.cuda.current_stream(self.device).synchronize()
         else:
             torch.cuda.synchronize()
+
+
+class VoiceFront:
+    """What VC.pipeline computes of a track before the voice model matters (VC.front): the filtered track and its chunk plan (`audio`,
+    `audio_pad`, `opt_ts`, `p_len`, `bounds`: what plan / chunk_bounds return), the UNTRANSPOSED f0 contour in Hz of the padded track
+    (`f0`: float64 (p_len,), the estimate as it left the _estimated_f0 seam -- no key shift, no coarse bins; None for if_f0 != 1) and
+    HuBERT's output per chunk (`feats`: [(1, T, C)], after final_proj for v1, before the retrieval mix, the x2 upsample and the protect
+    copy).  Everything lives on the device and is only read afterwards.  `key`: what it was built under; pipeline(front=) refuses a
+    front whose key differs from its own call in any field."""
+
+    FIELDS = ("audio_len", "audio_sum", "f0_method", "crepe_hop_length", "filter_radius", "if_f0", "version", "x_pad", "x_query",
+              "x_center", "x_max")
+
+    def __init__(self, key, audio, audio_pad, opt_ts, p_len, bounds, f0, feats, schedule):
+        self.key, self.audio, self.audio_pad, self.opt_ts, self.p_len, self.bounds = key, audio, audio_pad, opt_ts, p_len, bounds
+        self.f0, self.feats, self.schedule = f0, feats, schedule
+
+    def nbytes(self):
+        ts = [self.audio, self.audio_pad] + ([self.f0] if self.f0 is not None else []) + list(self.feats)
+        return sum(t.numel() * t.element_size() for t in ts)
+
+    def check(self, key):
+        for f in self.FIELDS:
+            if self.key[f] != key[f]:
+                raise ValueError("pipeline(front=): the front was built for %s = %r, this call has %r" % (f, self.key[f], key[f]))
 
 
 class VC(object):
@@ -262,13 +288,10 @@ class VC(object):
             self.model_rmvpe = RMVPE(self.rmvpe_path or self._default_rmvpe_path(), is_half=self.is_half, device=self.device)
         return self.model_rmvpe
 
-    def get_f0(self, input_audio_path, x, p_len, f0_up_key, f0_method, filter_radius, crepe_hop_length, inp_f0=None,
-               _raw_f0=None):
-        """-> (f0_coarse int64 (n,), f0 float64 (n,)) (reference :262-370).  `_raw_f0` (internal): the estimator's output
-        when pipeline() has already run it on a side stream."""
+    def _estimate_f0(self, input_audio_path, x, p_len, f0_method, filter_radius, crepe_hop_length, _raw_f0=None):
+        """The estimator's half of get_f0: the untransposed f0 track in Hz (numpy float64), passed through the _estimated_f0 seam.  Nothing
+        here depends on the voice: get_f0 goes on with the key shift and the coarse bins, VC.front keeps the track as it is."""
         f0_min, f0_max = 50, 1100
-        f0_mel_min = 1127 * np.log(1 + f0_min / 700)
-        f0_mel_max = 1127 * np.log(1 + f0_max / 700)
         def host(a):   # the crepe branches start with host numpy arithmetic (quantile normalisation), like the reference
             return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
 
@@ -288,8 +311,14 @@ class VC(object):
             raise NotImplementedError(
                 "f0_method %r needs parselmouth / pyworld, which are outside the MI355X hot path "
                 "(supported: rmvpe, mangio-crepe[-tiny], crepe[-tiny], hybrid[...] of the crepe methods)" % f0_method)
+        return np.asarray(self._estimated_f0(0, len(f0), np.asarray(f0, dtype=np.float64)), dtype=np.float64)
+
+    def get_f0(self, input_audio_path, x, p_len, f0_up_key, f0_method, filter_radius, crepe_hop_length, inp_f0=None,
+               _raw_f0=None):
+        """-> (f0_coarse int64 (n,), f0 float64 (n,)) (reference :262-370).  `_raw_f0` (internal): the estimator's output
+        when pipeline() has already run it on a side stream."""
+        f0 = self._estimate_f0(input_audio_path, x, p_len, f0_method, filter_radius, crepe_hop_length, _raw_f0)
         tf0 = self.sr // self.window
-        f0 = np.asarray(self._estimated_f0(0, len(f0), np.asarray(f0, dtype=np.float64)), dtype=np.float64)
         factor = pow(2, f0_up_key / 12)
         if inp_f0 is not None:
             f0 = f0 * factor
@@ -346,9 +375,15 @@ class VC(object):
         return self._vc_features_many(model, [audio0], index, big_npy, index_rate, version, use_protect)[0]
 
     def _vc_features_many(self, model, audios, index, big_npy, index_rate, version, use_protect):
-        """_vc_features for several chunks -> [(feats, feats0)].  A model with `extract_features_many` (aicovergen_amd.hubert) runs
-        the transformer's per-token layers once over all chunks; any other object with fairseq's `extract_features` is called
-        chunk by chunk, as the reference does."""
+        """_vc_features for several chunks -> [(feats, feats0)]: the HuBERT half (_hubert_many, which needs neither the voice nor the pitch)
+        and, chunk by chunk, the voice's half (_vc_features_post)."""
+        return [self._vc_features_post(model, lg, index, big_npy, index_rate, version, use_protect)
+                for lg in self._hubert_many(model, audios, version)]
+
+    def _hubert_many(self, model, audios, version):
+        """HuBERT's hidden states of several chunks (layer 9 for v1 models, 12 for v2), before final_proj.  A model with
+        `extract_features_many` (aicovergen_amd.hubert) runs the transformer's per-token layers once over all chunks; any other object
+        with fairseq's `extract_features` is called chunk by chunk, as the reference does."""
         srcs = []
         for audio0 in audios:
             # audio0: host array (reference contract) or a slice of the track already resident on the device
@@ -359,20 +394,28 @@ class VC(object):
             srcs.append(feats.view(1, -1).to(self.device))
         layer = 9 if version == "v1" else 12
         if len(srcs) > 1 and hasattr(model, "extract_features_many"):
-            logits = model.extract_features_many(srcs, layer)
-        else:
-            logits = [model.extract_features(source=s, padding_mask=torch.zeros(s.shape, dtype=torch.bool), output_layer=layer)[0]
-                      for s in srcs]
-        return [self._vc_features_post(model, lg, index, big_npy, index_rate, version, use_protect) for lg in logits]
+            return model.extract_features_many(srcs, layer)
+        return [model.extract_features(source=s, padding_mask=torch.zeros(s.shape, dtype=torch.bool), output_layer=layer)[0]
+                for s in srcs]
 
     def _vc_features_post(self, model, logits, index, big_npy, index_rate, version, use_protect):
-        feats = model.final_proj(logits) if version == "v1" else logits
-        feats0 = feats.clone() if use_protect else None
-        if index is not None and hasattr(index, "mix_") and index_rate != 0:
+        return self._vc_features_voice(model.final_proj(logits) if version == "v1" else logits, index, big_npy, index_rate, use_protect)
+
+    def _vc_features_voice(self, feats, index, big_npy, index_rate, use_protect, shared=False):
+        """The voice's half of a chunk's features: the copy the protect blend needs and the retrieval mix -> (feats, feats0).
+        `shared`: `feats` belongs to a VoiceFront and other calls will read it again -- the device mix works in place, so it gets a copy,
+        and the untouched tensor itself serves as feats0."""
+        mix = index is not None and index_rate != 0
+        if shared:
+            feats0 = feats if use_protect else None
+            feats = feats.clone() if mix and hasattr(index, "mix_") else feats
+        else:
+            feats0 = feats.clone() if use_protect else None
+        if mix and hasattr(index, "mix_"):
             # device retrieval (aicovergen_amd.retrieval.FeatureIndex): faiss' search for the file's index type (IVF-Flat with
             # its nprobe, or flat) + inverse-square blend, all in HBM
             feats = index.mix_(feats[0].contiguous(), index_rate).unsqueeze(0)
-        elif index is not None and big_npy is not None and index_rate != 0:
+        elif mix and big_npy is not None:
             npy = feats[0].cpu().numpy().astype("float32")
             score, ix = index.search(npy, k=8)
             weight = np.square(1 / score)
@@ -518,18 +561,27 @@ class VC(object):
         "1" = the recurrence as one launch.)  One rank on a GPU takes the progressive schedule too since the f0 chain became the longer
         branch of the phase (r4: HuBERT 74.9 ms, f0 79.4): the chunk loop then starts when HuBERT is done, on the middle chunks, while
         the recurrence finishes the track's ends -- 718.7 -> 713.9 ms per 240 s track at 8 segments (4: 715.5, 16: 715.6)."""
-        on_gpu = self._sync()
-        env_seg = int(_env.dev("AICG_F0_SEGMENTS", "0"))
-        nseg = env_seg or (16 if world > 1 else (8 if on_gpu else 0))
-        if not (if_f0 == 1 and f0_method == "rmvpe" and (on_gpu or nseg > 1) and _env.dev("AICG_OVERLAP_F0", "1") != "0"):
+        schedule, nseg = self._f0_schedule(if_f0, f0_method, world, inp_f0)
+        if schedule == "serial":
             return "serial", nseg, False
+        return schedule, nseg, self._two_streams(net_g)
+
+    def _two_streams(self, net_g):
         # Two streams: the encoder half of chunk i + 1 (text encoder + flow: ~140 short launches that leave most CUs idle and take the host
         # about as long to queue -- 40 us each -- as the GPU to run) is queued on a second stream underneath the vocoder of chunk i
         # (_chunk).  What that buys is small -- 2 ms per 240 s track: short launches running beside the vocoder cost it nearly what they
         # take alone (one stream: 674.7 ms, two: 667) -- and a stream priority changes nothing.  AICG_OVERLAP_SYNTH=0: one stream.
-        two_streams = on_gpu and hasattr(net_g, "infer_front") and _env.dev("AICG_OVERLAP_SYNTH", "1") != "0"
+        return self._sync() and hasattr(net_g, "infer_front") and _env.dev("AICG_OVERLAP_SYNTH", "1") != "0"
+
+    def _f0_schedule(self, if_f0, f0_method, world, inp_f0):
+        """-> (schedule, f0 segments): the part of _schedule that does not look at the voice model (VC.front takes the same decision)."""
+        on_gpu = self._sync()
+        env_seg = int(_env.dev("AICG_F0_SEGMENTS", "0"))
+        nseg = env_seg or (16 if world > 1 else (8 if on_gpu else 0))
+        if not (if_f0 == 1 and f0_method == "rmvpe" and (on_gpu or nseg > 1) and _env.dev("AICG_OVERLAP_F0", "1") != "0"):
+            return "serial", nseg
         # an f0 curve file (inp_f0) keeps the one-launch schedule, whose get_f0 splices it
-        return ("progressive" if nseg > 1 and inp_f0 is None else "one_launch"), nseg, two_streams
+        return ("progressive" if nseg > 1 and inp_f0 is None else "one_launch"), nseg
 
     def _run_f0(self, c, raw=None):
         pc, pcf = self.get_f0(*c.f0_args, _raw_f0=raw)
@@ -564,6 +616,92 @@ class VC(object):
         # one upload of the padded track: a pageable host->device copy on the default stream waits for the whole device,
         # side stream included, so the chunk loop must not issue any
         c.pad_dev = c.audio_pad.float()
+
+    # ---- whole track: what does not depend on the voice ---------------------------------------------------------------------------
+    def _front_key(self, audio, f0_method, crepe_hop_length, filter_radius, if_f0, version):
+        """What a VoiceFront is valid for.  The audio is identified by its length and the int64 sum of its float32 bit patterns -- exact in
+        any summation order, so a host array and its device copy give the same number; one reduction and a 8-byte read."""
+        if torch.is_tensor(audio):
+            a = audio.detach().float().contiguous().view(-1)
+            n, total = a.numel(), int(a.view(torch.int32).sum(dtype=torch.int64).item())
+        else:
+            a = np.ascontiguousarray(audio, dtype=np.float32).reshape(-1)
+            n, total = a.size, int(a.view(np.int32).sum(dtype=np.int64))
+        return {"audio_len": int(n), "audio_sum": total, "f0_method": f0_method, "crepe_hop_length": crepe_hop_length,
+                "filter_radius": filter_radius, "if_f0": if_f0, "version": version, "x_pad": self.x_pad, "x_query": self.x_query,
+                "x_center": self.x_center, "x_max": self.x_max}
+
+    def front(self, model, audio, input_audio_path, f0_method, if_f0, version, filter_radius, crepe_hop_length):
+        """Everything pipeline() computes of a track before the voice model matters -> VoiceFront: plan and chunk bounds, the f0 estimate
+        (untransposed) and HuBERT over every chunk.  pipeline(..., front=) then runs the voice's part only -- f0 tail, retrieval mix,
+        synthesizer -- and returns what the call without a front returns, bit for bit: this takes the f0 schedule pipeline() would take
+        (_f0_schedule; serial: the estimator through get_f0's first half and HuBERT chunk by chunk, overlapped: RMVPE on the side stream --
+        in the same segments, so the classifier GEMM sees the same frame ranges -- under HuBERT over all chunks at once), so every kernel
+        sees the shapes it sees there.  Never communicates (no process group).  A multi-workgroup BiGRU that timed out waiting for its
+        partners is rerun on the single-workgroup kernel here, as _settle / _recover do, before the front is handed out."""
+        key = self._front_key(audio, f0_method, crepe_hop_length, filter_radius, if_f0, version)
+        audio, audio_pad, opt_ts, p_len = self.plan(audio)
+        bounds = self.chunk_bounds(audio_pad, opt_ts)
+        schedule, nseg = self._f0_schedule(if_f0, f0_method, 1, None)
+        proj = (lambda lg: model.final_proj(lg)) if version == "v1" else (lambda lg: lg)
+        f0 = f0_dev = None
+        if schedule == "serial":
+            if if_f0 == 1:
+                f0 = self._estimate_f0(input_audio_path, audio_pad, p_len, f0_method, filter_radius, crepe_hop_length)
+            feats = [proj(self._hubert_many(model, [audio_pad[s:e]], version)[0]) for s, e in bounds]
+        else:
+            c = _Call(device=self.device, on_gpu=self._sync(), window=self.window, audio_pad=audio_pad, bounds=bounds, p_len=p_len,
+                      schedule=schedule, nseg=nseg, noise_fn=None)
+            self._open_side(c)
+            if c.progressive:       # created on `main` before the side stream forks from it, like the pitch tracks of _f0_progressive
+                f0 = torch.zeros(p_len, dtype=torch.float64, device=self.device)
+
+            def on_f0(lo, hi, est):
+                est, hi = self._estimated_f0(lo, hi, est), min(hi, p_len)
+                if lo < hi:
+                    f0[lo:hi] = est[: hi - lo]
+            c.side.wait_stream(c.main)
+            with (torch.cuda.stream(c.side) if c.on_gpu else c.side):      # RMVPE is queued before HuBERT
+                if c.progressive:
+                    self._rmvpe().infer_progressive(c.pad_dev, 0.03, nseg, on_f0)
+                else:
+                    f0_dev = self._rmvpe().infer_from_audio_device(c.pad_dev, thred=0.03)
+            feats = [proj(lg) for lg in self._hubert_many(model, [c.pad_dev[s:e] for s, e in bounds], version)]
+            c.main.synchronize()
+            c.side.synchronize()
+            c.main.wait_stream(c.side)
+            bad = c.progressive and self._rmvpe().last_segments.timed_out()
+            if ops.gru_timed_out() or bad:
+                warnings.warn("aicovergen_amd: the multi-workgroup BiGRU timed out waiting for its partner workgroups (busy or shared GPU); "
+                              "f0 is recomputed on the single-workgroup kernel", RuntimeWarning)
+                f0_dev = self._rmvpe().infer_from_audio_device(c.pad_dev, thred=0.03, two_workgroups=False)
+            if f0_dev is not None:
+                f0 = self._estimate_f0(input_audio_path, audio_pad, p_len, f0_method, filter_radius, crepe_hop_length,
+                                       _raw_f0=f0_dev.cpu().numpy())
+        if f0 is not None and not torch.is_tensor(f0):
+            f0 = torch.from_numpy(np.ascontiguousarray(f0[:p_len])).to(self.device)
+        if self._sync():
+            torch.cuda.synchronize()
+        return VoiceFront(key, audio, audio_pad, opt_ts, p_len, bounds, f0, feats, schedule)
+
+    def _f0_front(self, c):
+        """pipeline(front=): the voice's tail of the phase the front holds -- key shift and coarse bins of the cached contour (_f0_tail, on
+        the device), this call's retrieval mix and protect copy on the cached HuBERT output -- then the chunk loop of the overlapped
+        schedules, encoder halves on their own stream included."""
+        c.main = torch.cuda.current_stream(self.device) if c.on_gpu else _HostStream()
+        c.tf0 = ttime()
+        if c.if_f0 == 1:
+            f0bak, coarse = self._f0_tail(c.front.f0, pow(2, c.f0_args[3] / 12))      # f0_up_key
+            c.pitch, c.pitchf = coarse.unsqueeze(0), f0bak.float().unsqueeze(0)
+        tf1 = ttime()
+        use_protect = c.protect < 0.5 and c.if_f0 == 1
+        c.feats_of = {ci: self._vc_features_voice(c.front.feats[ci], c.index, c.big_npy, c.index_rate, use_protect, shared=True)
+                      for ci in c.mine}
+        self._open_enc(c)
+        c.main.synchronize()
+        c.t2 = ttime()
+        c.times[0] += c.t2 - tf1
+        c.times[1] += tf1 - c.tf0
 
     def _f0_one_launch(self, c):
         """f0 on the side stream with the recurrence as one launch, every chunk's features on `main` on top of it; the host joins both."""
@@ -726,7 +864,7 @@ class VC(object):
     @_bracket_pipeline
     def pipeline(self, model, net_g, sid, audio, input_audio_path, times, f0_up_key, f0_method, file_index, index_rate,
                  if_f0, filter_radius, tgt_sr, resample_sr, rms_mix_rate, version, protect, crepe_hop_length, f0_file=None,
-                 noise_fn=None, group=None, noise_seed=None, device_out=False):
+                 noise_fn=None, group=None, noise_seed=None, device_out=False, front=None):
         """Same contract as the reference (:474-653): float32 16 kHz mono in, int16 at tgt_sr out (`device_out`: as an int16 tensor left
         on the device, for a caller that goes on there; the samples are the same).
         `noise_fn(chunk_index, start, end) -> (noise_z, noise_src)` injects the synthesizer noise (tests); `noise_seed`
@@ -734,26 +872,39 @@ class VC(object):
         distributed over ranks UP TO fp32 SUMMATION ORDER: the HuBERT transformer runs once over all of a rank's chunks
         (HubertModel.extract_features_many), so the GEMM tiles -- and the order of their fp32 sums -- depend on how many chunks a
         rank owns; outputs of different world sizes agree to ~1e-6 relative (tests/test_dist.py states the bound), ranks of one run
-        agree bit for bit; `group` shards the chunk loop over the ranks of a torch.distributed process group."""
+        agree bit for bit; `group` shards the chunk loop over the ranks of a torch.distributed process group.
+        `front`: a VoiceFront of this audio (VC.front, same f0 method and model version): plan, f0 estimate and HuBERT are taken from it
+        and only the voice's part runs -- the same samples, bit for bit.  ValueError if it was built for something else (the field is
+        named), or together with an f0 curve file or a process group."""
+        if front is not None and (f0_file is not None or group is not None):
+            raise ValueError("pipeline(front=) does not take %s" % ("an f0_file curve" if f0_file is not None else "a process group"))
         if noise_fn is None and noise_seed is not None:
             noise_fn = self._seeded_noise(net_g, noise_seed)
         index, big_npy = self._load_index(file_index, index_rate)
         self._group = group   # the crepe f0 methods shard their frames over it, RMVPE its U-Net
         tp0 = ttime()
-        audio, audio_pad, opt_ts, p_len = self.plan(audio)
+        if front is None:
+            audio, audio_pad, opt_ts, p_len = self.plan(audio)
+        else:
+            front.check(self._front_key(audio, f0_method, crepe_hop_length, filter_radius, if_f0, version))
+            audio, audio_pad, opt_ts, p_len = front.audio, front.audio_pad, front.opt_ts, front.p_len
         t1 = ttime()
         inp_f0 = self._read_f0_file(f0_file) if hasattr(f0_file, "name") else None
         sid = torch.tensor(sid, device=self.device).unsqueeze(0).long()
-        bounds = self.chunk_bounds(audio_pad, opt_ts)
+        bounds = self.chunk_bounds(audio_pad, opt_ts) if front is None else front.bounds
         rank, world = adist.world(group)
-        schedule, nseg, two_streams = self._schedule(net_g, if_f0, f0_method, world, inp_f0)
+        if front is None:
+            schedule, nseg, two_streams = self._schedule(net_g, if_f0, f0_method, world, inp_f0)
+        else:
+            schedule, nseg, two_streams = "front", 0, self._two_streams(net_g)
         c = _Call(device=self.device, on_gpu=self._sync(), window=self.window, model=model, net_g=net_g, sid=sid, index=index,
                   big_npy=big_npy, index_rate=index_rate, version=version, protect=protect, if_f0=if_f0, noise_fn=noise_fn, times=times,
                   f0_args=(input_audio_path, audio_pad, p_len, f0_up_key, f0_method, filter_radius, crepe_hop_length, inp_f0),
                   audio_pad=audio_pad, bounds=bounds, mine=[ci for ci in range(len(bounds)) if ci % world == rank], p_len=p_len,
-                  schedule=schedule, nseg=nseg, two_streams=two_streams, t1=t1)
+                  schedule=schedule, nseg=nseg, two_streams=two_streams, t1=t1, front=front)
         # f0 and features: queued (overlapped schedules) or done (serial) when this returns; c.t2 is set
-        {"serial": self._f0_serial, "one_launch": self._f0_one_launch, "progressive": self._f0_progressive}[schedule](c)
+        {"serial": self._f0_serial, "one_launch": self._f0_one_launch, "progressive": self._f0_progressive,
+         "front": self._f0_front}[schedule](c)
         self._chunk_loop(c)
         if c.progressive and (ops.gru_timed_out() or c.f0_bad):
             self._recover(c)
@@ -767,6 +918,8 @@ class VC(object):
         self.last_profile = {"plan_s": t1 - tp0, "f0_s": c.t2 - t1, "chunks_s": tc1 - c.t2, "post_s": ttime() - tc1,
                              "f0_wait_s": c.f0_wait, "overlap_f0": float(c.overlap), "join_s": tj1 - tc1,
                              "f0_progressive": float(c.progressive)}
+        if front is not None:       # f0_s above: the voice's tail of the front's phase
+            self.last_profile["front_reused"] = 1.0
         return audio_opt
 
 

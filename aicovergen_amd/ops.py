@@ -677,7 +677,11 @@ def layernorm_ct(x, gamma, beta, res=None, out=None, eps=1e-5):
 
 def rownorm_act(x, gamma, beta, act=ACT_NONE, eps=1e-5, out=None):
     """x: (rows, T), unit stride along T: per-row (x - mean)/sqrt(var + eps) * gamma + beta, then act.  x (and out) may be views of rows
-    padded to a common stride (x.stride(0) >= T); `out` defaults to a buffer laid out like x."""
+    padded to a common stride (x.stride(0) >= T); `out` defaults to a buffer laid out like x.  The padding is neither read nor written.
+    Layout and bits: rows shorter than 4096 give the same bits for every stride.  Longer rows take the split form, which cuts a row into
+    head scalars, a 16-byte-aligned float4 body and tail scalars by the row's address and merges the parts' moments in that order, so
+    a row gives the same bits under two strides only where (row * stride) % 4 agrees; otherwise the two results differ by the fp32
+    rounding of the moment merge (each within the kernel's error against float64; tests/test_rownorm_padded.py)."""
     assert x.dim() == 2 and (x.stride(1) == 1 or x.shape[1] == 1)
     rows, t = x.shape
     ld = x.stride(0) if rows > 1 else max(x.stride(0), t)

@@ -2,6 +2,7 @@
 src/mdx.py:257,273,280 and src/my_utils.py:14-16; none of them exist in this image).  scipy only; no arithmetic
 beyond sample-format conversion and (if a file is not at the requested rate) polyphase resampling."""
 import shutil
+import struct
 import subprocess
 
 import numpy as np
@@ -50,6 +51,46 @@ def load_wav(path, sr, mono):
         g = np.gcd(int(file_sr), int(sr))
         x = resample_poly(x, sr // g, file_sr // g, axis=1).astype(np.float32)
     return (x[0] if mono else x), sr
+
+
+def wav_rate(path):
+    """Sample rate the fmt chunk of a RIFF / RIFX / RF64 WAVE file states, whatever its sample encoding (only the chunk headers in front
+    of it are read: the samples stay on disk); None for anything else."""
+    try:
+        with open(path, "rb") as f:
+            head = f.read(12)
+            if len(head) < 12 or head[:4] not in (b"RIFF", b"RIFX", b"RF64") or head[8:] != b"WAVE":
+                return None
+            order = ">" if head[:4] == b"RIFX" else "<"
+            while True:
+                chunk = f.read(8)
+                if len(chunk) < 8:
+                    return None
+                size = struct.unpack(order + "I", chunk[4:])[0]
+                if chunk[:4] == b"fmt ":
+                    return struct.unpack(order + "HHI", f.read(8))[2]     # format tag, channels, rate
+                f.seek(size + (size & 1), 1)                              # chunks are padded to an even length
+    except (OSError, struct.error):
+        return None
+
+
+def load_device(path, sr, device):
+    """-> float32 (channels, N) tensor at `sr` on `device`: load_wav(path, sr, mono=False) with the sample-format conversion and the
+    resampling done on the device (ops.resample_poly: the same polyphase filter, in float32).  A plain WAV file is uploaded in its file
+    format -- 16-bit PCM as int16 (frames, channels), every other encoding as the float32 _to_float makes of it; anything scipy cannot
+    parse is decoded by ffmpeg, which already delivers `sr`."""
+    import torch
+    from . import ops
+    try:
+        file_sr, data = wavfile.read(path)
+    except Exception:
+        return torch.from_numpy(np.ascontiguousarray(load_wav(path, sr, mono=False)[0], dtype=np.float32)).to(device)
+    data = data[:, None] if data.ndim == 1 else data
+    if data.dtype == np.int16:
+        x = torch.from_numpy(np.ascontiguousarray(data)).to(device)                  # (frames, C): read as x / 32768 by the kernel
+    else:
+        x = torch.from_numpy(np.ascontiguousarray(_to_float(data).T)).to(device)      # (C, frames)
+    return ops.resample_poly(x, int(file_sr), int(sr))
 
 
 def write_wav_pcm16(path, data, sr):

@@ -485,7 +485,7 @@ class CoverSession:
     """The models of a cover, loaded once: the three MDX-Net sessions (model_data.json entries looked up by hash, as run_mdx does),
     HuBERT, and a small cache of voice models by directory name.  A second song through the same session reloads nothing."""
 
-    def __init__(self, mdxnet_models_dir, rvc_models_dir, output_dir, device=None):
+    def __init__(self, mdxnet_models_dir, rvc_models_dir, output_dir, device=None, resample_sr=0):
         import json
         from . import mdx, rvc
         self.mdxnet_models_dir, self.rvc_models_dir, self.output_dir = mdxnet_models_dir, rvc_models_dir, output_dir
@@ -499,6 +499,9 @@ class CoverSession:
         self.profile_stages = False      # True: drain the device after every stage and keep the wall-clock split in last_profile
         self.last_profile = {}
         self.song = None                 # the last song's voice-independent part (_Song); capacity: one song
+        # VC.pipeline's resample_sr (rvc_infer passes 0): >= 16000 and not the voice's rate -> the AI vocals are resampled to it on the
+        # device.  Not part of a cached song: it acts behind the voice-independent front.
+        self.resample_sr = int(resample_sr)
 
     def drop_song(self):
         """Forget the cached song: its stems, hand-over, shifted stems and fronts leave device memory."""
@@ -536,8 +539,11 @@ class CoverSession:
         from . import audio_io, mdx
         dev = self.mdx_sessions[0].device
         base = os.path.splitext(os.path.basename(song_path))[0]
-        wave, sr = audio_io.load_wav(song_path, 44100, mono=False)
-        song = torch.from_numpy(np.ascontiguousarray(wave, dtype=np.float32)).to(dev)
+        if audio_io.wav_rate(song_path) in (None, 44100):
+            wave, sr = audio_io.load_wav(song_path, 44100, mono=False)
+            song = torch.from_numpy(np.ascontiguousarray(wave, dtype=np.float32)).to(dev)
+        else:       # a WAV file at another rate: uploaded as it is, converted and resampled on the device (run_mdx takes the same route)
+            song, sr = audio_io.load_device(song_path, 44100, dev), 44100
         path = lambda stem: os.path.join(song_dir, "%s_%s.wav" % (base, stem))
         vocals, inst = mdx.run_mdx_device(self.mdx_sessions[0], song, True)
         fetch.add(_write_wavfile, path("Instrumental"), inst, sr)
@@ -570,9 +576,9 @@ class CoverSession:
                 song.fronts[key] = vc.front(self.hubert, audio, dereverb_path, f0_method, if_f0, version, filter_radius, crepe_hop_length)
             front = song.fronts[key]
         out = vc.pipeline(self.hubert, net_g, 0, audio, dereverb_path, [0, 0, 0], pitch_change, f0_method, index_path, index_rate,
-                          if_f0, filter_radius, tgt_sr, 0, rms_mix_rate, version, protect, crepe_hop_length,
+                          if_f0, filter_radius, tgt_sr, self.resample_sr, rms_mix_rate, version, protect, crepe_hop_length,
                           noise_seed=noise_seed, device_out=True, front=front)
-        return out, tgt_sr
+        return out, (self.resample_sr if self.resample_sr >= 16000 and self.resample_sr != tgt_sr else tgt_sr)
 
     def song_cover_pipeline(self, song_input, voice_model, pitch_change, keep_files, is_webui=0, main_gain=0, backup_gain=0,
                             inst_gain=0, index_rate=0.5, filter_radius=3, rms_mix_rate=0.25, f0_method='rmvpe', crepe_hop_length=128,
@@ -830,6 +836,9 @@ def build_parser():
     p.add_argument("-rdry", "--reverb-dryness", type=float, default=0.8, help="Reverb dry level between 0 and 1")
     p.add_argument("-rdamp", "--reverb-damping", type=float, default=0.7, help="Reverb damping between 0 and 1")
     p.add_argument("-oformat", "--output-format", type=str, default="mp3", help="Output format of audio file. mp3 for smaller file size, wav for best quality")
+    # Not one of main.py's flags.  SUPPRESS keeps it out of the parsed namespace unless given, so a command line of main.py's parses to
+    # exactly main.py's namespace (tests/test_cover_pipeline.py compares the two whole); main() reads it with a default of 0.
+    p.add_argument("-osr", "--resample-sr", type=int, default=argparse.SUPPRESS, help="Sample rate of the AI vocals (>= 16000); 0 or absent: the voice model's own rate")
     p.add_argument("--mdx-models-dir", type=str, default=os.path.join(BASE_DIR, "mdxnet_models"), help="Directory of the MDX-Net .onnx files and model_data.json")
     p.add_argument("--rvc-models-dir", type=str, default=os.path.join(BASE_DIR, "rvc_models"), help="Directory of hubert_base.pt, rmvpe.pt and the voice model folders")
     p.add_argument("--output-dir", type=str, default=os.path.join(BASE_DIR, "song_output"), help="Directory the song_id folders are made in")
@@ -842,7 +851,7 @@ def main(argv=None):
     for name in dirnames:
         if not os.path.exists(os.path.join(args.rvc_models_dir, name)):
             raise Exception(f"The folder {os.path.join(args.rvc_models_dir, name)} does not exist.")
-    session = CoverSession(args.mdx_models_dir, args.rvc_models_dir, args.output_dir)
+    session = CoverSession(args.mdx_models_dir, args.rvc_models_dir, args.output_dir, resample_sr=getattr(args, "resample_sr", 0))
     shared = dict(main_gain=args.main_vol, backup_gain=args.backup_vol,
                   inst_gain=args.inst_vol, index_rate=args.index_rate, filter_radius=args.filter_radius, rms_mix_rate=args.rms_mix_rate,
                   f0_method=args.pitch_detection_algo, crepe_hop_length=args.crepe_hop_length, protect=args.protect,

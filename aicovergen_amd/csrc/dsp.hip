@@ -4,9 +4,13 @@
 //   * zero-phase IIR (scipy.signal.filtfilt, float64)     -- the 48 Hz high-pass of VC.pipeline (:513)
 //   * polyphase FIR resampling (scipy.signal.resample_poly semantics) + channel mean -- the 44.1 kHz stereo -> 16 kHz mono hand-over
 //     between run_mdx and rvc_infer that the reference does through a WAV file and ffmpeg (mdx.py:273,280; my_utils.py:14-16)
+//   * the same per channel, fp32, table and input tile in LDS -- a song file or a converted track at any sample rate (librosa.load's
+//     resampling at mdx.py:257, librosa.resample at vc_infer_pipeline.py:641-644)
 //   * exact k = 8 nearest neighbours + inverse-square-distance feature mix -- index.search / big_npy blend (:409-431)
 // All HBM-bound except the kNN distances, which run on the conv kernel as a 1x1 GEMM (ops.py).
 #include "common.h"
+
+#include <cstdint>
 
 namespace aicg {
 
@@ -134,6 +138,146 @@ __global__ void __launch_bounds__(256) resample_poly_kernel(const float* __restr
         acc += (double)hrow[j] * (double)(nch > 1 ? s * inv : s);
     }
     y[i] = (float)acc;
+}
+
+// ---- polyphase resampling, every channel for itself ---------------------------------------------------------------------------------
+// y[c][i] = sum_m h[(i + pre) * down - m * up] * x[c][m], the same upfirdn form and the same table hp[phase][tap] as above, without
+// the channel mean and in fp32: a song file or a converted track brought to another rate (48 kHz <-> 44.1 kHz, 40 kHz -> 48 kHz).
+// HBM-streaming with a small reused operand, so both operands of the inner product are read from LDS:
+//   * the table is copied once per workgroup, which then walks over tiles of T outputs (grid-stride), so the copy is paid once per
+//     ~20 tiles on a 4-minute track and not per tile;
+//   * consecutive outputs use the phases ((i + pre) * down) mod up, which jump by `down mod up` through the table -- for 441 / 320
+//     that is 320 = 0 mod 32 rows, every lane of a wave on one bank whatever the row padding.  The LDS copy is therefore stored in
+//     the ORDER OF USE: row k holds phase (k * down) mod up (a bijection, gcd(up, down) = 1), so output i reads row (i + pre) mod up
+//     and the lanes of a wave read consecutive rows (the sequence wraps at most once per wave).  Rows are reversed (ascending m)
+//     and padded to a stride of S floats with S / 4 odd: a lane reads its row as 16-byte groups, a 16-byte LDS read is served 16 lanes at
+//     a time over 64 banks, and 16 consecutive rows at a stride of 4 * odd dwords cover the 16 four-bank slots exactly once;
+//   * the input tile is staged with 16-byte loads (4 frames per lane; zeros outside [0, n_in)), each lane then reads its window
+//     x[m_hi - taps + 1 .. m_hi] as dwords: neighbouring lanes start 0, 1 or 2 frames apart (down / up frames on average), so a
+//     wave's 32-lane read groups touch nearly consecutive banks;
+//   * lane l of the workgroup produces outputs l, l + 256, ... of the tile: every store is a wave's 256 contiguous bytes;
+//   * no division in the loops: (m_hi, phase row, table row) of a lane's output advance from tile to tile and from output to
+//     output by constant (quotient, remainder) pairs.
+// One fmaf chain per output in ascending m: a fixed order, results are run-to-run identical and do not depend on the tiling.
+struct __attribute__((aligned(4))) rs_float4_u { float x, y, z, w; };   // 16 bytes at any float's address (row c starts at c * n_in)
+struct __attribute__((aligned(8))) rs_short4 { short x, y, z, w; };
+struct __attribute__((aligned(16))) rs_short8 { short a0, b0, a1, b1, a2, b2, a3, b3; };
+
+constexpr int kRsPcm16 = 0, kRsF32 = 1;   // in_format, as aicg_stem_normalise's
+constexpr int kRsThreads = 256;
+constexpr int kRsMaxRate = 1 << 20;       // up and down (gcd-reduced sample rates) the entry point accepts
+
+struct RsArgs {
+    long n_in, n_out, pre;
+    int C, up, down, taps, S, T, xs_len;
+};
+
+// (q, r) += (dq, dr) in the mixed radix (., up): r stays in [0, up)
+__device__ __forceinline__ void rs_advance(long& q, int& r, long dq, int dr, int up) {
+    q += dq;
+    r += dr;
+    if (r >= up) { r -= up; ++q; }
+}
+
+template <int FMT>
+__device__ __forceinline__ float rs_load1(const void* __restrict__ x, const RsArgs& a, int c, long m) {
+    if (m < 0 || m >= a.n_in) return 0.f;
+    if (FMT == kRsF32) return ((const float*)x)[(long)c * a.n_in + m];
+    return (float)((const short*)x)[m * a.C + c] * (1.0f / 32768.0f);   // a power of two: the exact quotient
+}
+
+template <int FMT>
+__global__ void __launch_bounds__(kRsThreads) resample_poly_mc_kernel(const void* __restrict__ x, float* __restrict__ y,
+                                                                      const float* __restrict__ hp, RsArgs a) {
+    HIP_DYNAMIC_SHARED(float4, smem4)
+    float* tab = reinterpret_cast<float*>(smem4);   // [up][S]
+    float* xs = tab + (long)a.up * a.S;             // [xs_len]; up * S is a multiple of 4: 16-byte aligned
+    const int tid = threadIdx.x, c = blockIdx.y;
+    const int up = a.up, down = a.down, taps = a.taps, S = a.S, T = a.T;
+
+    for (int e = tid; e < up * S; e += kRsThreads) {
+        const int row = e / S, k = e - row * S;
+        const int phase = (int)(((long)row * down) % up);
+        tab[e] = k < taps ? hp[(long)phase * taps + (taps - 1 - k)] : 0.f;
+    }
+
+    // this lane's first output of the workgroup's first tile: t = (i + pre) * down = mh * up + rem, table row (i + pre) mod up
+    const long i_first = (long)blockIdx.x * T;
+    long mh0, mht;           // m_hi of the tile's first output / of this lane's
+    int r0, rt, rowt;
+    {
+        const long t0 = (i_first + a.pre) * down, tt = (i_first + tid + a.pre) * down;
+        mh0 = t0 / up; r0 = (int)(t0 - mh0 * up);
+        mht = tt / up; rt = (int)(tt - mht * up);
+        rowt = (int)((i_first + tid + a.pre) % up);
+    }
+    const long tile_step = (long)gridDim.x * T;                       // outputs between two tiles of one workgroup
+    const long tile_dq = (tile_step * down) / up;
+    const int tile_dr = (int)((tile_step * down) % up), tile_drow = (int)(tile_step % up);
+    const int out_dq = (kRsThreads * down) / up, out_dr = (kRsThreads * down) % up, out_drow = kRsThreads % up;
+    float* yc = y + (long)c * a.n_out;
+
+    for (long i0 = i_first; i0 < a.n_out; i0 += tile_step) {
+        const long m_base = ((mh0 - taps + 1) >> 2) << 2;             // floor to a multiple of 4 (also below zero)
+        __syncthreads();                                              // the previous tile has been read (first pass: nothing)
+        for (int g = tid; g < a.xs_len / 4; g += kRsThreads) {
+            const long m = m_base + 4L * g;
+            float4 v;
+            if (m >= 0 && m + 4 <= a.n_in && (FMT == kRsF32 || a.C <= 2)) {
+                if (FMT == kRsF32) {
+                    const rs_float4_u u = *reinterpret_cast<const rs_float4_u*>((const float*)x + (long)c * a.n_in + m);
+                    v = make_float4(u.x, u.y, u.z, u.w);
+                } else if (a.C == 1) {
+                    const rs_short4 u = *reinterpret_cast<const rs_short4*>((const short*)x + m);
+                    const float k = 1.0f / 32768.0f;
+                    v = make_float4((float)u.x * k, (float)u.y * k, (float)u.z * k, (float)u.w * k);
+                } else {
+                    const rs_short8 u = *reinterpret_cast<const rs_short8*>((const short*)x + 2 * m);
+                    const float k = 1.0f / 32768.0f;
+                    v = c == 0 ? make_float4((float)u.a0 * k, (float)u.a1 * k, (float)u.a2 * k, (float)u.a3 * k)
+                               : make_float4((float)u.b0 * k, (float)u.b1 * k, (float)u.b2 * k, (float)u.b3 * k);
+                }
+            } else {
+                v = make_float4(rs_load1<FMT>(x, a, c, m), rs_load1<FMT>(x, a, c, m + 1), rs_load1<FMT>(x, a, c, m + 2),
+                                rs_load1<FMT>(x, a, c, m + 3));
+            }
+            reinterpret_cast<float4*>(xs)[g] = v;
+        }
+        __syncthreads();
+
+        long mh = mht;
+        int r = rt, row = rowt;
+        for (int o = tid; o < T; o += kRsThreads) {
+            if (i0 + o < a.n_out) {
+                const float* xw = xs + (int)(mh - taps + 1 - m_base);   // in [0, xs_len - taps]: the host sized xs_len for it
+                const float4* hr = reinterpret_cast<const float4*>(tab + row * S);
+                float acc = 0.f;
+                int k = 0;
+                for (; k + 4 <= taps; k += 4) {
+                    const float4 h = hr[k >> 2];
+                    acc = fmaf(h.x, xw[k], acc);
+                    acc = fmaf(h.y, xw[k + 1], acc);
+                    acc = fmaf(h.z, xw[k + 2], acc);
+                    acc = fmaf(h.w, xw[k + 3], acc);
+                }
+                if (k < taps) {
+                    const float4 h = hr[k >> 2];
+                    acc = fmaf(h.x, xw[k], acc);
+                    if (k + 1 < taps) acc = fmaf(h.y, xw[k + 1], acc);
+                    if (k + 2 < taps) acc = fmaf(h.z, xw[k + 2], acc);
+                }
+                yc[i0 + o] = acc;
+            }
+            rs_advance(mh, r, out_dq, out_dr, up);
+            row += out_drow;
+            if (row >= up) row -= up;
+        }
+
+        rs_advance(mh0, r0, tile_dq, tile_dr, up);
+        rs_advance(mht, rt, tile_dq, tile_dr, up);
+        rowt += tile_drow;
+        if (rowt >= up) rowt -= up;
+    }
 }
 
 // ---- k = 8 nearest neighbours + mix ---------------------------------------------------------------------------------------------------
@@ -371,6 +515,52 @@ extern "C" int aicg_resample_poly(const float* x, float* y, int64_t n_in, int64_
     hipLaunchKernelGGL(resample_poly_kernel, dim3((unsigned)ldiv_up(n_out, 256)), dim3(256), 0, (hipStream_t)stream, x, y, (long)n_in,
                        (long)n_out, n_channels, (long)x_sc, up, down, hp, taps, (long)pre);
     return check_launch("resample_poly_kernel");
+}
+
+extern "C" int aicg_resample_poly_mc(const void* x, int in_format, float* y, int n_channels, int64_t n_in, int64_t n_out, int up, int down,
+                                     const float* hp, int taps, int64_t pre, void* stream) {
+    if (in_format != kRsPcm16 && in_format != kRsF32)
+        return fail(AICG_E_ARG, "aicg_resample_poly_mc: input format %d (0 = int16 frames x channels, 1 = float32 channels x frames)", in_format);
+    if (up < 1 || down < 1 || taps < 1 || pre < 0)
+        return fail(AICG_E_ARG, "aicg_resample_poly_mc: bad rate / filter geometry (up %d, down %d, taps %d, pre %lld)", up, down, taps, (long long)pre);
+    // With frame counts and `pre` below 2^40 and the rates at most 2^20, every product of the geometry -- n_in * up, (i + pre) * down,
+    // a tile step * down, and kRsThreads * down as an int -- stays far inside its type, here and in the kernel.
+    const long lds_floats = 160 * 1024 / 4;
+    if (down > kRsMaxRate)
+        return fail(AICG_E_ARG, "aicg_resample_poly_mc: down %d (at most %d)", down, kRsMaxRate);
+    if (up > kRsMaxRate || taps > lds_floats)
+        return fail(AICG_E_LDS, "aicg_resample_poly_mc: a table of %d phases x %d taps exceeds the 160 KiB LDS", up, taps);
+    if (n_channels < 1 || n_channels > 65535 || n_in < 0 || n_out < 0 || n_in >= (1L << 40) || n_out >= (1L << 40) || pre >= (1L << 40))
+        return fail(AICG_E_SHAPE, "aicg_resample_poly_mc: %d channels, %lld -> %lld frames", n_channels, (long long)n_in, (long long)n_out);
+    if (n_out > ((long)n_in * up + down - 1) / down)
+        return fail(AICG_E_SHAPE, "aicg_resample_poly_mc: %lld outputs asked of %lld frames at %d / %d (at most ceil(n_in up / down))",
+                    (long long)n_out, (long long)n_in, up, down);
+    // row stride: the taps rounded up to whole 16-byte groups, an odd number of them (bank spread of the row-per-lane reads)
+    int S = (taps + 3) & ~3;
+    if (((S >> 2) & 1) == 0) S += 4;
+    // the largest tile whose input window fits beside the table; a lane's window may start up to 3 frames behind the aligned base
+    int T = 0, xs_len = 0;
+    for (int t = 4 * kRsThreads; t >= kRsThreads; t >>= 1) {
+        const long need = (((long)(up - 1) + (long)(t - 1) * down) / up + taps + 3 + 3) & ~3L;
+        if ((long)up * S + need <= lds_floats) { T = t; xs_len = (int)need; break; }
+    }
+    if (!T)
+        return fail(AICG_E_LDS, "aicg_resample_poly_mc: a table of %d phases x %d taps and the input of %d outputs at %d / %d exceed the 160 KiB LDS",
+                    up, taps, kRsThreads, up, down);
+    if (n_out == 0) return AICG_OK;
+    if (!x && n_in > 0) return fail(AICG_E_ARG, "aicg_resample_poly_mc: null pointer");
+    if (!y || !hp) return fail(AICG_E_ARG, "aicg_resample_poly_mc: null pointer");
+    if (in_format == kRsPcm16 && ((uintptr_t)x & 15)) return fail(AICG_E_ARG, "aicg_resample_poly_mc: a 16-bit PCM input must be 16-byte aligned");
+    RsArgs a;
+    a.n_in = (long)n_in; a.n_out = (long)n_out; a.pre = (long)pre;
+    a.C = n_channels; a.up = up; a.down = down; a.taps = taps; a.S = S; a.T = T; a.xs_len = xs_len;
+    const size_t lds = sizeof(float) * ((size_t)up * S + xs_len);
+    const long tiles = ldiv_up((long)n_out, T);
+    const dim3 grid((unsigned)lmin(tiles, lmax(1, 2048 / n_channels)), (unsigned)n_channels);
+    auto kern = in_format == kRsF32 ? resample_poly_mc_kernel<kRsF32> : resample_poly_mc_kernel<kRsPcm16>;
+    allow_dynamic_lds((const void*)kern, lds);
+    hipLaunchKernelGGL(kern, grid, dim3(kRsThreads), lds, (hipStream_t)stream, x, y, hp, a);
+    return check_launch("resample_poly_mc_kernel");
 }
 
 extern "C" int aicg_row_sqnorm(const float* v, float* out, int64_t rows, int dim, void* stream) {

@@ -285,7 +285,10 @@ def run_mdx(model_params, output_dir, model_path, filename, exclude_main=False, 
                      stem_name=entry["primary_stem"], compensation=entry["compensate"])
     session = MDX(model_path, model)
 
-    wave, sr = audio_io.load_wav(filename, 44100, mono=False)
+    if audio_io.wav_rate(filename) in (None, 44100):
+        wave, sr = audio_io.load_wav(filename, 44100, mono=False)
+    else:   # a WAV file at another rate: converted and resampled on the device, as CoverSession._separate does (the same samples)
+        wave, sr = audio_io.load_device(filename, 44100, device).cpu().numpy(), 44100
     if wave.shape[0] == 1:
         wave = np.concatenate([wave, wave], 0)
     peak = max(np.max(wave), abs(np.min(wave)))

@@ -1362,6 +1362,26 @@ def resample_poly_mono(x, sr_in, sr_out):
     return y
 
 
+def resample_poly(x, sr_in, sr_out):
+    """(C, n) float32 or (n, C) int16 PCM (read as x / 32768) device signal at sr_in -> (C, n_out) float32 at sr_out, every channel
+    for itself: scipy.signal.resample_poly(x, up, down, axis=1) with its default filter and trimming, n_out = ceil(n up / down).
+    sr_in == sr_out: the input as float32, nothing is launched."""
+    if x.dim() != 2 or x.dtype not in (torch.float32, torch.int16):
+        raise TypeError("resample_poly takes (channels, n) float32 or (frames, channels) int16, got %s %s" % (x.dtype, tuple(x.shape)))
+    pcm = x.dtype == torch.int16
+    if int(sr_in) == int(sr_out):
+        return x.t().float().mul_(1.0 / 32768.0).contiguous() if pcm else x
+    if not x.is_contiguous():
+        raise ValueError("resample_poly takes a contiguous tensor (strides %s of shape %s)" % (x.stride(), tuple(x.shape)))
+    n, c = (x.shape[0], x.shape[1]) if pcm else (x.shape[1], x.shape[0])
+    up, down, table, taps, pre, n_out = _resample_plan(sr_out, sr_in, n, x.device)
+    y = torch.empty((c, n_out), dtype=torch.float32, device=x.device)
+    _check(x, table)
+    _call("aicg_resample_poly_mc", _ptr(x), STEM_PCM16 if pcm else STEM_F32, _ptr(y), c, n, n_out, up, down, _ptr(table), taps, pre,
+          _stream(x))
+    return y
+
+
 def row_sqnorm(v):
     v = v.contiguous().float()
     out = torch.empty(v.shape[0], dtype=torch.float32, device=v.device)

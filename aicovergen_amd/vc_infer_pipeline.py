@@ -842,18 +842,14 @@ class VC(object):
     def _post(self, audio_opt, audio, tgt_sr, resample_sr, rms_mix_rate, device_out=False):
         """The joined float32 track at tgt_sr -> the call's int16 result: RMS mix with the input, peak limit, truncating cast (reference :639-651).
         `device_out`: the int16 tensor stays on the device (the same samples) instead of being copied to a host array."""
-        if resample_sr >= 16000 and tgt_sr != resample_sr:
-            # optional output resampling (rvc_infer passes resample_sr=0): host fallback, not on the hot path
-            a = audio_opt.cpu().numpy()
-            if rms_mix_rate != 1:
-                a = change_rms(audio.cpu().numpy(), 16000, a, tgt_sr, rms_mix_rate)
-            g = np.gcd(int(tgt_sr), int(resample_sr))
-            audio_opt = torch.from_numpy(signal.resample_poly(a, resample_sr // g, tgt_sr // g).astype(np.float32)).to(self.device)
-        elif rms_mix_rate != 1:
+        if rms_mix_rate != 1:
             # change_rms on the device: frame RMS envelopes (1 s frames, 0.5 s hop), linear interpolation, power mix
             rms1 = ops.frame_rms(audio, 16000 // 2 * 2, 16000 // 2)
             rms2 = ops.frame_rms(audio_opt, tgt_sr // 2 * 2, tgt_sr // 2)
             ops.rms_mix_(audio_opt, rms1, rms2, rms_mix_rate)
+        if resample_sr >= 16000 and tgt_sr != resample_sr:
+            # optional output resampling (rvc_infer passes resample_sr=0), after change_rms as in the reference (:639-644)
+            audio_opt = ops.resample_poly(audio_opt[None], tgt_sr, resample_sr)[0]
         audio_max = float(ops.absmax(audio_opt).item()) / 0.99
         max_int16 = 32768
         if audio_max > 1:

@@ -375,6 +375,17 @@ int aicg_filtfilt_f64(const double* x, double* y, int64_t n, const double* b, co
 int aicg_resample_poly(const float* x, float* y, int64_t n_in, int64_t n_out, int n_channels, int64_t x_sc, int up, int down,
                        const float* hp, int taps, int64_t pre, void* stream);
 
+/* The same sum for every channel separately, in fp32: y[c][i] = sum_m h[(i + pre) * down - m * up] * x[c][m], hp as above.  A song
+ * file or a converted track at another sample rate (librosa.load's resampling at src/mdx.py:257, librosa.resample at
+ * src/vc_infer_pipeline.py:641-644).  in_format as aicg_stem_normalise: 0 = 16-bit PCM [n_in][n_channels] read as x / 32768
+ * (16-byte aligned), 1 = fp32 [n_channels][n_in]; y is fp32 [n_channels][n_out], n_out <= ceil(n_in up / down) (AICG_E_SHAPE
+ * beyond, for n_channels < 1 or > 65535 and for n_in, n_out or pre >= 2^40; AICG_E_ARG for up, down or taps < 1, down > 2^20 and
+ * pre < 0).  One fmaf chain per output in ascending m:
+ * run-to-run identical, a channel's result does not depend on the others.  The table and an input tile live in LDS:
+ * AICG_E_LDS when up x taps (rows padded to an odd number of 16-byte groups) plus the input of 256 outputs exceed 160 KiB. */
+int aicg_resample_poly_mc(const void* x, int in_format, float* y, int n_channels, int64_t n_in, int64_t n_out, int up, int down,
+                          const float* hp, int taps, int64_t pre, void* stream);
+
 /* Retrieval mix of VC.vc (src/vc_infer_pipeline.py:409-431: index.search(npy, k=8), inverse-square weights, blend; the index is
  * the faiss IVF-Flat file read at :497-512):
  * aicg_row_sqnorm: |v_r|^2 of a (rows, dim) matrix;

@@ -349,7 +349,9 @@ using namespace aicg;
 
 extern "C" int aicg_tdf_pair_supported(int F, int H, int rows_per_ch) {
     const int nh = H / 32;
-    return (H % 32 == 0 && (nh == 2 || nh == 3 || nh == 4 || nh == 6 || nh == 8 || nh == 12) && F % 32 == 0 && rows_per_ch % 32 == 0) ? 1 : 0;
+    // F and rows_per_ch positive: 0 is a multiple of 32 too, and the kernel divides by rows_per_ch and reads a first x slab unconditionally
+    return (H % 32 == 0 && (nh == 2 || nh == 3 || nh == 4 || nh == 6 || nh == 8 || nh == 12) && F > 0 && F % 32 == 0 && rows_per_ch > 0 &&
+            rows_per_ch % 32 == 0) ? 1 : 0;
 }
 
 extern "C" int aicg_tdf_pair(const float* x, const float* w1_packed, const float* b1, const float* s1, const float* t1, const float* w2_packed,

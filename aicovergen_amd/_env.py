@@ -5,6 +5,8 @@ Supported in a user's process:
     AICG_HALF=1                  opt-in fp16 matrix arithmetic where the caller ALSO passes is_half=True (src/main.py:196 does): HuBERT's and the
                                  synthesizer's LDS-DMA staged layers take fp16 operands, fp32 activations / accumulation (ops.mark_half; the f0
                                  models, SineGen, attention and MDX-Net stay fp32).  Without it .half() is a no-op and everything is fp32
+    AICG_HALF_STORE=1            on top of AICG_HALF=1 (nothing alone): the vocoder's ResBlocks of the last two stages keep their activations in fp16
+                                 in HBM (csrc/conv1d_h.hip, ops.conv_h; DESIGN 2.7 "half storage") -- the reference's storage numerics, not a speed-up
     AICG_FORCE_COLLECTIVES=1     a one-rank process group runs every join through the real collectives (tests/test_rccl_one_rank.py)
     AICG_DEVICE_POST=1           src/run_main.py puts src/compat first on sys.path: main.py's `pedalboard` / `pedalboard.io` / `pydub` imports
                                  resolve to device stand-ins (aicovergen_amd.cover), so add_audio_effects and combine_audio run without those

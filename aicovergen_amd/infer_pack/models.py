@@ -81,12 +81,14 @@ class _SynthesizerBase:
         # The reference runs fp16 on GPU (src/rvc.py:137-138).  Default: fp32 kernels (>= that precision); with AICG_HALF=1 the layers on
         # the LDS-DMA staged kernels take fp16 operands on the matrix pipe (ops.mark_half; fp32 activations and accumulation)
         self._half = ops.half_requested()
+        # ... and with AICG_HALF_STORE=1 on top, the ResBlocks of the vocoder's HBM-side stages keep their activations in fp16 (_decoder)
+        self._half_store = self._half and ops.half_store_requested()
         if self._p is not None:
             ops.mark_half(self._p, self._half)
         return self
 
     def float(self):
-        self._half = False
+        self._half = self._half_store = False
         if self._p is not None:
             ops.mark_half(self._p, False)
         return self
@@ -387,6 +389,10 @@ class _SynthesizerBase:
             # accumulating convolutions stay ordered k = 3, 7, 11 by events -- output bit-identical to the one-stream walk
             # (tests/test_synth.py).  Measured (tools/kbench_rb_streams.py, round-robin): chunk loop 238.1 ms against 237.8 -- the
             # launches do not overlap usefully (two resident workgroups per CU either way), so the one-stream walk stays the default.
+            if self._half_store_stage(P, i, nk):
+                self._resblocks_half_store(P["resblocks"][i * nk: (i + 1) * nk], x, acc)
+                x = acc
+                continue
             streams = self._rb_streams(x.device, nk)
             main = torch.cuda.current_stream(x.device) if streams else None
             bufs = [tuple(torch.empty_like(x) for _ in range(3)) for _ in range(nk if streams else 1)]
@@ -431,6 +437,36 @@ class _SynthesizerBase:
             x = acc
         # F.leaky_relu default slope 0.01 (models.py:513), conv_post (no bias), tanh
         return ops.conv(x, P["conv_post"], pre_act=ops.ACT_LRELU, pre_slope=0.01, act=ops.ACT_TANH, plan_w=plan(T * rate))
+
+    # Stages whose ResBlocks run with fp16 activations in HBM under AICG_HALF=1 + AICG_HALF_STORE=1 (after .half()): the LAST this many.
+    # At 40 kHz those are the 64- and 32-channel stages, whose k = 3 layers the Winograd kernel runs at the HBM's pace; the wider stages
+    # are bound by the matrix pipe and keep the fp16-operand kernels ("half storage").
+    HALF_STORE_STAGES = 2
+
+    def _half_store_stage(self, P, i, nk):
+        if not getattr(self, "_half_store", False) or i < len(P["ups"]) - self.HALF_STORE_STAGES:
+            return False
+        return all(pc.conv_h_supported() for convs in P["resblocks"][i * nk: (i + 1) * nk] for pair in convs for pc in pair if pc is not None)
+
+    def _resblocks_half_store(self, blocks, x, acc):
+        """The stage's ResBlock sum acc = mean_j resblock_j(x), the one-stream walk of _decoder on csrc/conv1d_h.hip: x (the transposed
+        convolution's output) and acc are fp32, every activation between them crosses HBM as fp16."""
+        nk = len(blocks)
+        tmp, ya, yb = (torch.empty(x.shape, dtype=torch.float16, device=x.device) for _ in range(3))
+        for j, convs in enumerate(blocks):
+            y = x
+            for m, (c1, c2) in enumerate(convs):
+                if c2 is None:  # ResBlock2
+                    src, inp, pre = c1, y, ops.ACT_LRELU
+                else:           # c1's epilogue applies c2's input activation once per element, as in the fp32 walk
+                    ops.conv_h(y, c1, out=tmp, pre_act=ops.ACT_LRELU, pre_slope=LRELU_SLOPE, act=ops.ACT_LRELU, act_slope=LRELU_SLOPE)
+                    src, inp, pre = c2, tmp, ops.ACT_NONE
+                if m == len(convs) - 1:
+                    ops.conv_h(inp, src, res=y, out=acc, pre_act=pre, pre_slope=LRELU_SLOPE, out_scale=1.0 / nk, accumulate=j > 0)
+                else:
+                    dst = ya if y is not ya else yb
+                    ops.conv_h(inp, src, res=y, out=dst, pre_act=pre, pre_slope=LRELU_SLOPE)
+                    y = dst
 
     def _rb_streams(self, device, nk):
         """Side streams for the ResBlock chains of a vocoder stage (one per chain but the first, created once per model: the caching

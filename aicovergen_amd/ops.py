@@ -168,6 +168,12 @@ def half_requested():
     return os.environ.get("AICG_HALF", "0") == "1"
 
 
+def half_store_requested():
+    """AICG_HALF=1 AND AICG_HALF_STORE=1: the vocoder's ResBlocks additionally keep their activations in fp16 in HBM on the stages routed
+    to csrc/conv1d_h.hip (conv_h).  A variable of its own: a run that only asks for fp16 operands (AICG_HALF=1) stays as it is."""
+    return half_requested() and os.environ.get("AICG_HALF_STORE", "0") == "1"
+
+
 def mark_half(tree, on=True):
     """Set / clear the fp16-operand flag on every PackedConv reachable from `tree` (dicts, lists, tuples, PackedConvTranspose)."""
     if isinstance(tree, PackedConv):
@@ -356,6 +362,30 @@ class PackedConv:
                 self._wino2_src, self._wino2_dev, self._wino2_images = weight.detach(), device, {}
                 self.w_wino2 = self.wino2_image(_w2d_code()[1])
 
+        # half-storage kernel (conv_h): its fp16 image is built on first use from the caller's own weight tensor (a reference, normally
+        # host memory) -- a layer that never takes that route carries nothing
+        self._h_src, self._h_dev, self._h_image = None, device, None
+        if (not self.split and not self.fp32_only and self.kh == 1 and self.kw in (3, 5, 7, 11) and groups == 1 and stride == (1, 1) and self.padding_end is None
+                and padding == (0, (self.kw - 1) // 2 * dilation[1])):
+            self._h_src = weight.detach()
+
+    def conv_h_supported(self):
+        """This layer has a half-storage form (aicg_conv1d_h_supported; never for fp32_only or split-precision layers)."""
+        return self._h_src is not None and bool(_lib.get().aicg_conv1d_h_supported(self.cin, self.cout, self.kw, self.dilation[1]))
+
+    def conv_h_image(self):
+        """aicg_conv1d_h's w_packed: fp16 (round to nearest even) [Cout_pad / 32][Cin / 8][k][2][32][4], built on first use."""
+        if self._h_image is None:
+            assert self.conv_h_supported(), "conv_h: layer has no half-storage form"
+            w = self._h_src.to(device=self._h_dev, dtype=torch.float32)[:, :, 0]
+            cout, cin, k = w.shape
+            cpad = 32 if cout <= 32 else -(-cout // 64) * 64
+            wp = torch.zeros(cpad, cin, k, dtype=torch.float32, device=w.device)
+            wp[:cout] = w
+            # (m, i, g, h, e, tap) -> (m, g, tap, h, i, e)
+            self._h_image = wp.reshape(cpad // 32, 32, cin // 8, 2, 4, k).permute(0, 2, 5, 3, 1, 4).contiguous().half()
+        return self._h_image
+
     def wino2_image(self, kind):
         """The F(2 x 2, 3 x 3) weight image with "dword" / "pairs" / "quads" fragments (winograd2d_image)."""
         if kind not in self._wino2_images:
@@ -524,6 +554,36 @@ def conv(x, pc, res=None, out=None, pre_act=ACT_NONE, pre_slope=0.0, act=ACT_NON
             n, c, pc.cout, h, w, pc.kh, pc.kw, pc.stride[0], pc.stride[1], pc.dilation[0], pc.dilation[1], pc.groups,
             " res" if r4 is not None else "", " acc" if accumulate else "", (" shuf" if shuffle else "") + (" wino2" if wino2 else " wino" if wino else " wino1d" if wino1 else "")),
             2.0 * n * pc.cout * (pc.cin // pc.groups) * pc.kh * pc.kw * ho * wo))
+    return out
+
+
+def conv_h(x, pc, res=None, out=None, out_dtype=torch.float16, pre_act=ACT_NONE, pre_slope=0.0, act=ACT_NONE, act_slope=0.0,
+           out_scale=1.0, accumulate=False):
+    """conv's formula, y = [y +] out_scale * (act(conv(pre_act(x)) + bias) + res), on the half-storage kernel (csrc/conv1d_h.hip):
+    x, res and out (N, C, T), last dim contiguous, are each fp16 or fp32; a new output is allocated as `out_dtype`.  Products on the
+    fp16 matrix pipe, everything else fp32, one rounding at an fp16 store."""
+    assert x.dim() == 3 and x.shape[1] == pc.cin, "conv_h: input (N, %d, T) expected, got %s" % (pc.cin, tuple(x.shape))
+    n, c, t = x.shape
+    for name, a in (("x", x), ("res", res), ("out", out)):
+        assert a is None or a.dtype in (torch.float16, torch.float32), "conv_h: %s is %s" % (name, a.dtype)
+        assert a is None or a.stride(2) == 1 or t == 1, "conv_h: %s rows must be contiguous" % name
+    if out is None:
+        assert not accumulate
+        out = torch.empty((n, pc.cout, t), dtype=out_dtype, device=x.device)
+    assert tuple(out.shape) == (n, pc.cout, t), (tuple(out.shape), (n, pc.cout, t))
+    assert res is None or res.shape == out.shape
+    if out.numel() == 0:
+        return out
+    if not pc.conv_h_supported():    # the library's message, without a launch
+        _check(x, out, res, pc.bias)
+        _call("aicg_conv1d_h", _ptr(x), 0, _ptr(pc.bias), _ptr(res), _ptr(out), n, c, pc.cout, t, pc.kw, pc.dilation[1], 0, 0, 0,
+              0, 0, 0, 0, 0, 0, pre_act, pre_slope, act, act_slope, out_scale, 0, _stream(x))
+    w = pc.conv_h_image()
+    _check(x, out, res, w, pc.bias)
+    h = lambda a: int(a is not None and a.dtype == torch.float16)
+    _call("aicg_conv1d_h", _ptr(x), _ptr(w), _ptr(pc.bias), _ptr(res), _ptr(out), n, c, pc.cout, t, pc.kw, pc.dilation[1],
+          h(x), h(res), h(out), x.stride(0), x.stride(1), 0 if res is None else res.stride(0), 0 if res is None else res.stride(1),
+          out.stride(0), out.stride(1), pre_act, pre_slope, act, act_slope, out_scale, 1 if accumulate else 0, _stream(x))
     return out
 
 

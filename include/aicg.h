@@ -311,6 +311,21 @@ int aicg_tdf_pair_supported(int F, int H, int rows_per_ch);
 int aicg_tdf_pair(const float* x, const float* w1_packed, const float* b1, const float* s1, const float* t1, const float* w2_packed,
                   const float* b2, const float* s2, const float* t2, float* out, int64_t R, int F, int H, int rows_per_ch,
                   int n_ch, void* stream);
+/* Half-storage 1-D convolution of the vocoder's ResBlocks (csrc/conv1d_h.hip), direct form on the fp16 matrix pipe:
+ *   out = [out +] out_scale * (act(conv_{k, dilation}(pre_act(x)) + bias) + res),  "same" zero padding (k - 1) / 2 * dilation.
+ * x (N, Cin, T), res and out (N, Cout, T): T contiguous, batch / channel strides in ELEMENTS; each operand is fp16 (its *_f16
+ * flag nonzero) or fp32 in memory, aligned to its element only.  res may be NULL; bias (fp32) may be NULL.
+ * w_packed: the weights rounded to fp16 (nearest even) as [Cout_pad / 32][Cin / 8][k][2][32][4], element e of (m, g, tap, h, i) =
+ * W[32 m + i][8 g + 4 h + e][tap], rows >= Cout zero; Cout_pad = 32 for Cout <= 32, else Cout rounded up to a multiple of 64;
+ * 16-byte aligned.  pre_act / act: AICG_ACT_NONE or AICG_ACT_LRELU, applied in fp32; the pre-activated input is rounded to fp16 once
+ * per element; accumulation, bias, activation, residual and scale are fp32; an fp16 out is rounded once at the store.
+ * aicg_conv1d_h_supported: 1 for Cin, Cout multiples of 16, k in {3, 5, 7, 11}, dilation in {1, 3, 5}; aicg_conv1d_h returns
+ * AICG_E_ARG for anything else (and for other activations, N > 65535, T >= 2^31 - 2^16) without launching. */
+int aicg_conv1d_h_supported(int cin, int cout, int k, int dilation);
+int aicg_conv1d_h(const void* x, const void* w_packed, const float* bias, const void* res, void* out, int N, int Cin, int Cout,
+                  int64_t T, int k, int dilation, int x_f16, int res_f16, int out_f16, int64_t x_sn, int64_t x_sc, int64_t r_sn,
+                  int64_t r_sc, int64_t o_sn, int64_t o_sc, int pre_act, float pre_slope, int act, float act_slope,
+                  float out_scale, int accumulate, void* stream);
 /* out = a * b elementwise (U-Net skip connection of the TFC-TDF net: x *= ds_outputs[-i-1]) */
 int aicg_mul(const float* a, const float* b, float* out, int64_t n, void* stream);
 /* run_mdx epilogue pieces (src/mdx.py:259-267,280): out = alpha * a + beta * b (+ gamma * c if c) */

@@ -1286,6 +1286,101 @@ def resample_ratio(x, ratio, n_out):
 
 
 # ---------------------------------------------------------------------------------------------------
+# f0_method "pm" (csrc/pitch_ac.hip): Praat's autocorrelation pitch
+# ---------------------------------------------------------------------------------------------------
+PITCH_AC_CANDIDATES = 15        # Praat's defaults behind parselmouth's to_pitch_ac
+PITCH_AC_SILENCE = 0.03
+PITCH_AC_OCTAVE_COST = 0.01
+PITCH_AC_OCTAVE_JUMP_COST = 0.35
+PITCH_AC_VOICED_UNVOICED_COST = 0.14
+
+
+def pitch_ac_geometry(sr, n, time_step=0.01, pitch_floor=50.0, pitch_ceiling=1100.0):
+    """(nsamp_window, nsampFFT, maximumLag, brent_ixmax, n_frames, floor(t1 in samples), candidate scratch bytes, path scratch bytes).
+    ValueError for a signal shorter than one window."""
+    g = (ctypes.c_int64 * 8)()
+    try:
+        _lib.call("aicg_pitch_ac_geometry", int(sr), int(n), float(time_step), float(pitch_floor), float(pitch_ceiling), ctypes.addressof(g))
+    except RuntimeError as e:
+        raise ValueError(str(e))
+    return tuple(int(v) for v in g)
+
+
+def pitch_ac_frame_times(sr, n, time_step=0.01, pitch_floor=50.0, pitch_ceiling=1100.0):
+    """Centre of every frame in seconds, float64 (n_frames,): (t1 + i time_step sr) / sr with t1 = n / 2 - (n_frames - 1) time_step sr / 2
+    in samples, exactly as the kernels place the frames (the geometry call returns floor(t1) only)."""
+    n_frames = pitch_ac_geometry(sr, n, time_step, pitch_floor, pitch_ceiling)[4]
+    step = float(time_step) * float(sr)
+    return (0.5 * n - 0.5 * (n_frames - 1) * step + np.arange(n_frames, dtype=np.float64) * step) / float(sr)
+
+
+def pitch_ac_tables(nw, nfft, brent):
+    """(window, window_ac, twiddle) float32, computed in float64: the Hanning window 0.5 - 0.5 cos(2 pi i / (nw + 1)), i = 1 .. nw, its
+    autocorrelation over lags 0 .. brent normalised to 1 at lag 0, and exp(-2 pi i k / nfft) as (cos, -sin) pairs."""
+    w = 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(1, nw + 1, dtype=np.float64) / (nw + 1))
+    wr = np.fft.irfft(np.abs(np.fft.rfft(w, nfft)) ** 2, nfft)
+    wr = wr[:brent + 1] / wr[0]
+    a = 2.0 * np.pi * np.arange(nfft, dtype=np.float64) / nfft
+    tw = np.stack([np.cos(a), -np.sin(a)], axis=1)
+    return w.astype(np.float32), wr.astype(np.float32), tw.astype(np.float32)
+
+
+_pitch_ac_plans = {}
+
+
+def _pitch_ac_plan(nw, nfft, brent, device):
+    key = (nw, nfft, brent, str(device))
+    if key not in _pitch_ac_plans:
+        _pitch_ac_plans[key] = tuple(torch.from_numpy(t).to(device) for t in pitch_ac_tables(nw, nfft, brent))
+    return _pitch_ac_plans[key]
+
+
+def pitch_ac_candidates(x, sr=16000, time_step=0.01, pitch_floor=50.0, pitch_ceiling=1100.0, voicing_threshold=0.6,
+                        max_candidates=PITCH_AC_CANDIDATES, silence_threshold=PITCH_AC_SILENCE, octave_cost=PITCH_AC_OCTAVE_COST):
+    """x: 1-D fp32 -> (cand fp32 (n_frames, max_candidates, 2) = (frequency, strength), count int32 (n_frames,))."""
+    assert x.dim() == 1 and x.dtype == torch.float32 and x.is_contiguous()
+    nw, nfft, _, brent, n_frames, _, cs, _ = pitch_ac_geometry(sr, x.numel(), time_step, pitch_floor, pitch_ceiling)
+    window, wac, tw = _pitch_ac_plan(nw, nfft, brent, x.device)
+    scratch = torch.empty(cs, dtype=torch.uint8, device=x.device)
+    cand = torch.empty((n_frames, int(max_candidates), 2), dtype=torch.float32, device=x.device)
+    count = torch.empty((n_frames,), dtype=torch.int32, device=x.device)
+    _check(x, window, wac, tw)
+    _call("aicg_pitch_ac_candidates", _ptr(x), x.numel(), int(sr), float(time_step), float(pitch_floor), float(pitch_ceiling),
+          int(max_candidates), float(voicing_threshold), float(silence_threshold), float(octave_cost), _ptr(window), _ptr(wac), _ptr(tw),
+          _ptr(scratch), _ptr(cand), _ptr(count), _stream(x))
+    return cand, count
+
+
+def pitch_ac_path(cand, count, time_step=0.01, pitch_ceiling=1100.0, octave_cost=PITCH_AC_OCTAVE_COST,
+                  octave_jump_cost=PITCH_AC_OCTAVE_JUMP_COST, voiced_unvoiced_cost=PITCH_AC_VOICED_UNVOICED_COST, return_states=False):
+    """The best path through a candidate table (float64 accumulation) -> f0 float64 (n_frames,) [, chosen indices int32]."""
+    assert cand.dim() == 3 and cand.shape[2] == 2 and cand.dtype == torch.float32 and cand.is_contiguous()
+    assert count.shape == (cand.shape[0],) and count.dtype == torch.int32 and count.is_contiguous()
+    n_frames, K = cand.shape[:2]
+    scratch = torch.empty(n_frames * (16 * 2 * 8 + 16), dtype=torch.uint8, device=cand.device)
+    f0 = torch.empty((n_frames,), dtype=torch.float64, device=cand.device)
+    states = torch.empty((n_frames,), dtype=torch.int32, device=cand.device)
+    _check(cand, count)
+    _call("aicg_pitch_ac_path", _ptr(cand), _ptr(count), n_frames, K, float(time_step), float(pitch_ceiling), float(octave_cost),
+          float(octave_jump_cost), float(voiced_unvoiced_cost), _ptr(scratch), _ptr(f0), _ptr(states), _stream(cand))
+    return (f0, states) if return_states else f0
+
+
+def pitch_ac(x, sr=16000, time_step=0.01, pitch_floor=50.0, pitch_ceiling=1100.0, voicing_threshold=0.6,
+             max_candidates=PITCH_AC_CANDIDATES, silence_threshold=PITCH_AC_SILENCE, octave_cost=PITCH_AC_OCTAVE_COST,
+             octave_jump_cost=PITCH_AC_OCTAVE_JUMP_COST, voiced_unvoiced_cost=PITCH_AC_VOICED_UNVOICED_COST, return_candidates=False):
+    """Praat's `Sound: To Pitch (ac)...` (parselmouth's to_pitch_ac, src/vc_infer_pipeline.py:279-289) on the device.  x: 1-D float32 or
+    float64 (cast on the device) -> f0 in Hz float64 (n_frames,), 0 = unvoiced [, cand, count].  ValueError for a signal shorter than
+    one window (3 / pitch_floor seconds)."""
+    assert x.dim() == 1
+    x = x.contiguous().float()
+    cand, count = pitch_ac_candidates(x, sr, time_step, pitch_floor, pitch_ceiling, voicing_threshold, max_candidates, silence_threshold,
+                                      octave_cost)
+    f0 = pitch_ac_path(cand, count, time_step, pitch_ceiling, octave_cost, octave_jump_cost, voiced_unvoiced_cost)
+    return (f0, cand, count) if return_candidates else f0
+
+
+# ---------------------------------------------------------------------------------------------------
 # CREPE helpers
 # ---------------------------------------------------------------------------------------------------
 def frame_normalize(frames):

@@ -244,6 +244,18 @@ class VC(object):
             return stack[0]
         return np.nanmedian(stack, axis=0)   # like the reference, estimators of different lengths raise here
 
+    def get_f0_pm_computation(self, x, f0_min, f0_max, p_len):
+        """f0_method 'pm' (reference :279-294): Praat's autocorrelation pitch at the 10 ms step, voicing threshold 0.6, zero-padded to
+        p_len frames.  The track stays on the device (ops.pitch_ac); no weights, no communication: every rank computes the whole contour."""
+        xd = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
+        f0 = ops.pitch_ac(xd.to(self.device), self.sr, self.window / self.sr, float(f0_min), float(f0_max), 0.6)
+        pad_size = (p_len - len(f0) + 1) // 2
+        if pad_size < 0 or p_len - len(f0) - pad_size < 0:      # np.pad in the reference: "index can't contain negative values"
+            raise ValueError("f0_method pm: %d frames do not fit p_len %d" % (len(f0), p_len))
+        if pad_size > 0 or p_len - len(f0) - pad_size > 0:
+            f0 = torch.nn.functional.pad(f0, (pad_size, p_len - len(f0) - pad_size))
+        return f0.cpu().numpy()
+
     def _f0_group(self, explicit=True):
         """The process group the f0 estimators may communicate over.  Inside pipeline() the ranks of the job cut RMVPE's U-Net
         over time (rmvpe.E2E.features_sharded) and CREPE's frames (crepe.predict); a stand-alone get_f0 /
@@ -304,13 +316,15 @@ class VC(object):
                                                "tiny" if f0_method.endswith("tiny") else "full")
         elif f0_method in ("crepe", "crepe-tiny"):
             f0 = self.get_f0_official_crepe_computation(host(x), f0_min, f0_max, "tiny" if f0_method.endswith("tiny") else "full")
+        elif f0_method == "pm":
+            f0 = self.get_f0_pm_computation(x, f0_min, f0_max, p_len)
         elif "hybrid" in f0_method:
             f0 = self.get_f0_hybrid_computation(f0_method, input_audio_path, host(x), f0_min, f0_max, p_len, filter_radius,
                                                 crepe_hop_length, self.window / self.sr * 1000)
         else:
             raise NotImplementedError(
-                "f0_method %r needs parselmouth / pyworld, which are outside the MI355X hot path "
-                "(supported: rmvpe, mangio-crepe[-tiny], crepe[-tiny], hybrid[...] of the crepe methods)" % f0_method)
+                "f0_method %r needs pyworld, which is outside the MI355X hot path "
+                "(supported: rmvpe, pm, mangio-crepe[-tiny], crepe[-tiny], hybrid[...] of the crepe methods)" % f0_method)
         return np.asarray(self._estimated_f0(0, len(f0), np.asarray(f0, dtype=np.float64)), dtype=np.float64)
 
     def get_f0(self, input_audio_path, x, p_len, f0_up_key, f0_method, filter_radius, crepe_hop_length, inp_f0=None,

@@ -501,6 +501,43 @@ int aicg_stem_normalise(const void* x, int in_format, int n_channels, int64_t n,
 int aicg_mdx_stems_pcm16(const float* wave, const float* separated, const float* peak, float compensation, int64_t n,
                          int16_t* main_out, int16_t* inverted_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * f0_method "pm" (src/vc_infer_pipeline.py:279-294: parselmouth's Sound.to_pitch_ac): Praat's autocorrelation pitch, Boersma
+ * (1993), restated (csrc/pitch_ac.hip).  dx = 1 / sample_rate, all host arithmetic float64.
+ *
+ * aicg_pitch_ac_geometry (src/vc_infer_pipeline.py:279-294): geom[0..8) =
+ *   nsamp_window = 2 (floor(3 / pitch_floor / dx) / 2 - 1), nsampFFT (smallest power of two >= 1.5 nsamp_window),
+ *   maximumLag = min(nsamp_window / 3 + 2, nsamp_window), brent_ixmax = nsamp_window / 2,
+ *   n_frames = floor((n dx - 3 / pitch_floor) / time_step) + 1, floor(t1 / dx) with the frames centred in the signal
+ *   (t1 / dx = n / 2 - (n_frames - 1) time_step sample_rate / 2), the byte size of aicg_pitch_ac_candidates' scratch and
+ *   of aicg_pitch_ac_path's scratch.  AICG_E_SHAPE for a signal shorter than one window (n dx < 3 / pitch_floor) or an FFT above
+ *   4096 points; AICG_E_ARG for rates, steps or a pitch range that make no sense.
+ * aicg_pitch_ac_candidates (src/vc_infer_pipeline.py:279-294, the frame stage): x fp32 (n).  Frame i covers the nsamp_window samples
+ *   from floor(t1 / dx + i time_step sample_rate - 0.5) + 1 - nsamp_window / 2: mean removed, Hanning window, real autocorrelation
+ *   through a 2 x nsampFFT-point FFT in LDS, normalised by the window's own autocorrelation, maxima above voicing_threshold / 2 at lags
+ *   2 .. min(maximumLag, brent_ixmax) - 1, strength by sinc interpolation (depth 30), at most max_candidates - 1 kept (the
+ *   weakest by strength - octave_cost log2(pitch_floor / f) gives way), each refined by a 20-step golden-section search of the depth-70
+ *   interpolation.  window (nsamp_window), window_ac (brent_ixmax + 1, the window's normalised autocorrelation) and twiddle
+ *   (nsampFFT pairs cos, -sin of 2 pi k / nsampFFT) are fp32 tables the host rounds from float64.  cand (n_frames, max_candidates, 2)
+ *   fp32 = (frequency, strength), candidate 0 the unvoiced one (frequency 0, strength voicing_threshold + max(0, 2 - (local peak /
+ *   global peak) / (silence_threshold / (1 + voicing_threshold)))), unused slots zero; count (n_frames) int32.  fp32 arithmetic in
+ *   a fixed order: run-to-run identical.  2 <= max_candidates <= 16.
+ * aicg_pitch_ac_path (src/vc_infer_pipeline.py:279-294, Pitch_pathFinder behind to_pitch_ac, and :288 selected_array): the
+ *   best path through such a table, float64: a candidate is voiced iff 0 < f < pitch_ceiling; node value strength - octave_cost
+ *   log2(pitch_ceiling / f) if voiced, else the strength of the frame's candidate 0; transition cost 0 (unvoiced pair),
+ *   voiced_unvoiced_cost c (mixed), octave_jump_cost c |log2 f1 - log2 f2| (voiced pair), c = 0.01 / time_step; ties to the lowest
+ *   index.  f0_out (n_frames) float64 = the chosen candidates' frequencies as they stand in the table; state_out (n_frames) int32
+ *   their indices (may be NULL).  One wave walks the frames.
+ * ---------------------------------------------------------------------------------------------- */
+int aicg_pitch_ac_geometry(int sample_rate, int64_t n, double time_step, double pitch_floor, double pitch_ceiling, int64_t* geom);
+int aicg_pitch_ac_candidates(const float* x, int64_t n, int sample_rate, double time_step, double pitch_floor, double pitch_ceiling,
+                             int max_candidates, double voicing_threshold, double silence_threshold, double octave_cost,
+                             const float* window, const float* window_ac, const float* twiddle, void* scratch, float* cand,
+                             int* count, void* stream);
+int aicg_pitch_ac_path(const float* cand, const int* count, int64_t n_frames, int max_candidates, double time_step,
+                       double pitch_ceiling, double octave_cost, double octave_jump_cost, double voiced_unvoiced_cost, void* scratch,
+                       double* f0_out, int* state_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,8 +13,6 @@
 
 namespace aicg {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 struct AttnArgs {
     const float* q;
     const float* k;

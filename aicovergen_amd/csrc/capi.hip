@@ -57,9 +57,8 @@ extern "C" int aicg_abi_version(void) { return 5; }  // 2: aicg_conv_desc gained
 // of the device the benchmarks run on (clock under load is power-dependent).  Returns nothing useful in `out` beyond
 // keeping the accumulators alive; time it from the host.
 namespace aicg {
-typedef float pf32x16 __attribute__((ext_vector_type(16)));
 __global__ void __launch_bounds__(256) mfma_probe_kernel(float* out, int iters, float seed) {
-    pf32x16 a0, a1, a2, a3;
+    f32x16 a0, a1, a2, a3;
     for (int r = 0; r < 16; ++r) { a0[r] = seed; a1[r] = seed + 1.f; a2[r] = seed + 2.f; a3[r] = seed + 3.f; }
     float x = seed * (float)(threadIdx.x & 7) + 0.5f, y = 0.25f + seed;
     for (int i = 0; i < iters; ++i) {

@@ -25,6 +25,8 @@
 #endif
 
 namespace aicg {
+typedef float f32x16 __attribute__((ext_vector_type(16)));   // the accumulator tile of a 32 x 32 MFMA
+typedef float f32x4 __attribute__((ext_vector_type(4)));     // the accumulator tile of a 16 x 16 MFMA; a raw 16-byte buffer load
 
 // error plumbing: the C ABI returns negative codes and keeps a per-thread message for aicg_last_error()
 void set_error(const char* fmt, ...);
@@ -143,9 +145,8 @@ __device__ __forceinline__ float4 buf_load_f32x4_s(const BufRsrc& r, unsigned vo
 // The raw-buffer intrinsics are bound by name (the clang builtin __builtin_amdgcn_raw_buffer_load_b128 of ROCm 7.2 lowers to
 // a 32-bit load and splats it); the resource is the classic 4-dword descriptor {base[47:0], stride 0, num_records, flags}.
 typedef int buf_i32x4 __attribute__((ext_vector_type(4)));
-typedef float buf_f32x4 __attribute__((ext_vector_type(4)));
 __device__ float llvm_amdgcn_raw_buffer_load_f32(buf_i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.f32");
-__device__ buf_f32x4 llvm_amdgcn_raw_buffer_load_v4f32(buf_i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v4f32");
+__device__ f32x4 llvm_amdgcn_raw_buffer_load_v4f32(buf_i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v4f32");
 struct BufRsrc { buf_i32x4 d; };
 __device__ __forceinline__ BufRsrc make_buf(const void* base, unsigned num_bytes) {
     const unsigned long a = (unsigned long)base;
@@ -163,11 +164,11 @@ __device__ __forceinline__ float buf_load_f32_s(const BufRsrc& r, unsigned voff,
     return llvm_amdgcn_raw_buffer_load_f32(r.d, (int)voff, (int)soff, 0);
 }
 __device__ __forceinline__ float4 buf_load_f32x4_s(const BufRsrc& r, unsigned voff, unsigned soff) {   // dword-aligned address
-    const buf_f32x4 v = llvm_amdgcn_raw_buffer_load_v4f32(r.d, (int)voff, (int)soff, 0);
+    const f32x4 v = llvm_amdgcn_raw_buffer_load_v4f32(r.d, (int)voff, (int)soff, 0);
     return make_float4(v.x, v.y, v.z, v.w);
 }
 __device__ __forceinline__ float4 buf_load_f32x4(const BufRsrc& r, unsigned voff) {
-    const buf_f32x4 v = llvm_amdgcn_raw_buffer_load_v4f32(r.d, (int)voff, 0, 0);
+    const f32x4 v = llvm_amdgcn_raw_buffer_load_v4f32(r.d, (int)voff, 0, 0);
     return make_float4(v.x, v.y, v.z, v.w);
 }
 #endif
@@ -200,8 +201,7 @@ __device__ __forceinline__ void split_bf16_pair(float v0, float v1, unsigned& hi
 #endif
 }
 // 8 bf16 (k = 8 half .. 8 half + 7 of a 16-row K group) packed in a float4: element e in bits 16 (e & 1) of word e >> 1
-typedef float mfma_f32x16 __attribute__((ext_vector_type(16)));
-__device__ __forceinline__ mfma_f32x16 mfma_bf16_32x32x16(const float4& a, const float4& b, mfma_f32x16 c) {
+__device__ __forceinline__ f32x16 mfma_bf16_32x32x16(const float4& a, const float4& b, f32x16 c) {
 #ifdef AICG_EMULATED
     const unsigned aw[4] = {__builtin_bit_cast(unsigned, a.x), __builtin_bit_cast(unsigned, a.y), __builtin_bit_cast(unsigned, a.z),
                             __builtin_bit_cast(unsigned, a.w)};
@@ -239,7 +239,7 @@ __device__ __forceinline__ H4 pack_f16x4(float v0, float v1, float v2, float v3)
 #endif
     return r;
 }
-__device__ __forceinline__ mfma_f32x16 mfma_f16_32x32x8(const H4& a, const H4& b, mfma_f32x16 c) {
+__device__ __forceinline__ f32x16 mfma_f16_32x32x8(const H4& a, const H4& b, f32x16 c) {
 #ifdef AICG_EMULATED
     const unsigned aw[2] = {a.x, a.y}, bw[2] = {b.x, b.y};
     for (int e = 0; e < 4; ++e) {   // four two-row contractions of the fp32 MFMA model: lane half h supplies k = 4 h + e

@@ -67,7 +67,7 @@ __global__ void __launch_bounds__(256) conv1d_h_kernel(C1hArgs p) {
     const int mt0 = blockIdx.y * MT;
     const int ngroups = p.Cin / 8;
 
-    mfma_f32x16 acc[MT][2];
+    f32x16 acc[MT][2];
 #pragma unroll
     for (int m = 0; m < MT; ++m)
 #pragma unroll

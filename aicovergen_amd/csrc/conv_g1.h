@@ -1,6 +1,6 @@
 // 1 x 1 convolution (unit stride, no padding, one group, contiguous maps) as the plain GEMM it is,
 //     Y[M, P] = W[M, K] X[K, P]            M = Cout, K = Cin, P = H * W positions of one image,
-// with BOTH operands staged by LDS DMA and single-role waves -- what tdf_pair.hip (123-131 TFLOP/s) and conv_w2d.h showed for their shapes,
+// with BOTH operands staged by LDS DMA (lds_dma.h) and single-role waves -- what tdf_pair.hip (123-131 TFLOP/s) and conv_w2d.h showed for their shapes,
 // on a plain K loop.  VERDICT r3 item 1: the per-token GEMMs of HuBERT (768 <-> 3072 at 13 198 tokens: 66-86 TFLOP/s on the
 // producer / consumer kernel of conv_ws3.h), MDX-Net's up-sampling GEMM + pixel shuffle (58-70), the 1 x 1 layers of enc_p / flow / vocoder
 // (reference ops: src/infer_pack/attentions.py:190-193,387-388, the fairseq encoder behind src/rvc.py:98-109, src/mdx.py:74-77).
@@ -22,7 +22,8 @@
 // Zero padding -- channels past Cin, positions past the end of the map, rows past Mpad -- is the buffer range check's (offset
 // kBufOob, or past num_records).  Input activations other than a leaky ReLU stay on conv_ws3.
 #pragma once
-#include "conv_w2d.h"
+#include "conv_args.h"
+#include "lds_dma.h"
 
 namespace aicg {
 
@@ -30,13 +31,6 @@ static constexpr int kG1KS = 16;     // K rows per stage (two k-groups of 8)
 static constexpr int kG1Bufs = 3;
 
 __host__ __device__ constexpr int g1_stage_floats(int bm, int bn) { return kG1KS * (bm + bn); }
-
-template <int N>
-__device__ __forceinline__ void g1_wait_pieces() {   // at most N of this wave's DMA pieces still in flight
-#ifndef AICG_EMULATED
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-#endif
-}
 
 // Epilogue shared by conv_g1_kernel and conv_g1k_kernel.  Register r of tile (i, j): row m_wave0 + 32 i + 8 (r >> 2) + 4 half + (r & 3),
 // position pos + j (pos = the first of this lane's four consecutive positions; HW % 4 == 0: a quad is inside the map or outside).
@@ -201,8 +195,8 @@ __global__ void __launch_bounds__(256) AICG_WAVES_PER_SIMD(WPS) conv_g1_kernel(C
         xb = make_buf(ximg + (long)st * kG1KS * p.x_sc, (unsigned)lmin(left, 0x7fffffffL));
     };
     auto issue_piece = [&](int e, float* buf) __attribute__((always_inline)) {   // e < PA: weights, else positions
-        if (e < PA) w2d_dma16(wb, aoff[e], 0u, buf + (wave + 4 * e) * 256, lane);
-        else w2d_dma16(xb, boff[e - PA], 0u, buf + kG1KS * BM + (wave + 4 * (e - PA)) * 256, lane);
+        if (e < PA) dma16(wb, aoff[e], 0u, buf + (wave + 4 * e) * 256, lane);
+        else dma16(xb, boff[e - PA], 0u, buf + kG1KS * BM + (wave + 4 * (e - PA)) * 256, lane);
     };
     auto issue = [&](int st, float* buf) __attribute__((always_inline)) {
         stage_rsrc(st);
@@ -245,13 +239,13 @@ __global__ void __launch_bounds__(256) AICG_WAVES_PER_SIMD(WPS) conv_g1_kernel(C
             const H4 bh3 = pack_f16x4(pre(b[0].w), pre(b[1].w), pre(b[2].w), pre(b[3].w));
             auto piece_behind = [&](int blk) __attribute__((always_inline)) {
                 if constexpr (DMA) {
-                    w2d_fence();
+                    sched_fence();
                     if (more) {
 #pragma unroll
                         for (int e = 0; e < PW; ++e)
                             if (e * NBLK / PW == blk) issue_piece(e, fill);
                     }
-                    w2d_fence();
+                    sched_fence();
                 }
             };
 #pragma unroll
@@ -280,13 +274,13 @@ __global__ void __launch_bounds__(256) AICG_WAVES_PER_SIMD(WPS) conv_g1_kernel(C
                 acc[i][3] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv.w, acc[i][3], 0, 0, 0);
                 if constexpr (DMA) {
                     const int blk = s * TM + i;
-                    w2d_fence();
+                    sched_fence();
                     if (more) {
 #pragma unroll
                         for (int e = 0; e < PW; ++e)
                             if (e * NBLK / PW == blk) issue_piece(e, fill);
                     }
-                    w2d_fence();
+                    sched_fence();
                 }
             }
     };
@@ -299,32 +293,32 @@ __global__ void __launch_bounds__(256) AICG_WAVES_PER_SIMD(WPS) conv_g1_kernel(C
     float* b_nxt = smem + STAGE;
     float* b_fill = smem + 2 * STAGE;
     issue(0, b_cur);
-    if (nst > 1) { issue(1, b_nxt); g1_wait_pieces<PW>(); } else g1_wait_pieces<0>();
+    if (nst > 1) { issue(1, b_nxt); dma_wait<PW>(); } else dma_wait<0>();
     lds_barrier();
     float4 a0[TM], b0[4], a1[TM], b1[4];
     read_group(a0, b0, b_cur, 0);
     // (the last stage is peeled: a conditional mid-stage section would merge two LDS-counter states at its end, and hipcc then guards the
     //  second group's MFMAs with waits for the fragment reads issued a moment ago)
     for (int st = 0; st + 1 < nst; ++st) {
-        w2d_fence();
+        sched_fence();
         read_group(a1, b1, b_cur, 1);
-        w2d_fence();
+        sched_fence();
         mma_group(a0, b0, std::false_type{}, false, nullptr);
-        w2d_fence();
-        g1_wait_pieces<0>();   // this wave's pieces of stage st + 1 (the only ones in flight)
+        sched_fence();
+        dma_wait<0>();   // this wave's pieces of stage st + 1 (the only ones in flight)
         lds_barrier();
         const bool more = st + 2 < nst;
         if constexpr (SPREAD) { if (more) stage_rsrc(st + 2); } else { if (more) issue(st + 2, b_fill); }
         read_group(a0, b0, b_nxt, 0);
-        w2d_fence();
+        sched_fence();
         mma_group(a1, b1, std::integral_constant<bool, SPREAD>{}, more, b_fill);
         float* t = b_cur; b_cur = b_nxt; b_nxt = b_fill; b_fill = t;
     }
-    w2d_fence();
+    sched_fence();
     read_group(a1, b1, b_cur, 1);
-    w2d_fence();
+    sched_fence();
     mma_group(a0, b0, std::false_type{}, false, nullptr);
-    w2d_fence();
+    sched_fence();
     mma_group(a1, b1, std::false_type{}, false, nullptr);
 
     g1_epilogue<TM, SHUF>(p, acc, img, m_base + wm * (TM * 32), n0 + wn * 128 + 4 * l31, HW);

@@ -76,7 +76,7 @@ __global__ void __launch_bounds__(256) AICG_WAVES_PER_SIMD(WPS) conv_g1k_kernel(
         wb = make_buf(p.w3 + wbase, (unsigned)lmin((wtap - (long)cs * (kG1KS / 8) * 2 * p.Mpad * 4) * 4, 0x7fffffffL));
     };
     auto issue_a_piece = [&](int e, float* abuf) __attribute__((always_inline)) {
-        w2d_dma16(wb, aoff[e], 0u, abuf + (wave + 4 * e) * 256, lane);
+        dma16(wb, aoff[e], 0u, abuf + (wave + 4 * e) * 256, lane);
     };
     auto issue_a = [&](int cs, int t, float* abuf) __attribute__((always_inline)) {
         unit_rsrc(cs, t);
@@ -94,7 +94,7 @@ __global__ void __launch_bounds__(256) AICG_WAVES_PER_SIMD(WPS) conv_g1k_kernel(
             const int col = q - row * RQ;
             const int pos = s0 + 4 * col;
             const bool ok = q < nq && pos >= 0 && pos < T;
-            w2d_dma16(xb, ok ? 4u * (unsigned)(row * (int)p.x_sc + pos) : kBufOob, 0u, dst + piece * 256, lane);
+            dma16(xb, ok ? 4u * (unsigned)(row * (int)p.x_sc + pos) : kBufOob, 0u, dst + piece * 256, lane);
         }
     };
 
@@ -136,9 +136,9 @@ __global__ void __launch_bounds__(256) AICG_WAVES_PER_SIMD(WPS) conv_g1k_kernel(
                 bv.x = fmaxf(bv.x, bv.x * pre_slope); bv.y = fmaxf(bv.y, bv.y * pre_slope);
                 bv.z = fmaxf(bv.z, bv.z * pre_slope); bv.w = fmaxf(bv.w, bv.w * pre_slope);
             }
-            w2d_fence();
+            sched_fence();
             if constexpr (RELOAD) { bq0[s] = nxt[2 * s * RQ]; bq1[s] = nxt[2 * s * RQ + 1]; }
-            w2d_fence();
+            sched_fence();
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
                 const float av = s == 0 ? a[i].x : s == 1 ? a[i].y : s == 2 ? a[i].z : a[i].w;
@@ -148,13 +148,13 @@ __global__ void __launch_bounds__(256) AICG_WAVES_PER_SIMD(WPS) conv_g1k_kernel(
                 acc[i][3] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv.w, acc[i][3], 0, 0, 0);
                 if constexpr (DMA) {
                     const int blk = s * TM + i;
-                    w2d_fence();
+                    sched_fence();
                     if (more) {
 #pragma unroll
                         for (int e = 0; e < PA; ++e)
                             if (e * NBLK / PA == blk) issue_a_piece(e, fill);
                     }
-                    w2d_fence();
+                    sched_fence();
                 }
             }
         }
@@ -168,7 +168,7 @@ __global__ void __launch_bounds__(256) AICG_WAVES_PER_SIMD(WPS) conv_g1k_kernel(
     issue_b(0, bbuf);
     issue_a(0, 0, a_cur);
     if (nunits > 1) issue_a(0, 1, a_nxt);                // (k >= 2: unit 1 is tap 1 of channel stage 0)
-    g1_wait_pieces<0>();
+    dma_wait<0>();
     lds_barrier();
     float4 a0[TM], a1[TM];
     int sig = delta0;                                    // shift of the running unit's tap: t d + delta0
@@ -181,12 +181,12 @@ __global__ void __launch_bounds__(256) AICG_WAVES_PER_SIMD(WPS) conv_g1k_kernel(
     // (the last unit is peeled, as conv_g1.h peels its last stage: no conditional section inside the loop body)
     for (int u = 0; u + 1 < nunits; ++u) {
         const float* wcur = bbuf + (cs & 1) * BSTAGE;
-        w2d_fence();
+        sched_fence();
         read_a(a1, a_cur, 1);
-        w2d_fence();
+        sched_fence();
         mma_group(sig & 3, a0, window_ptr(wcur, 1, sig >> 2), std::true_type{}, std::false_type{}, false, nullptr);
-        w2d_fence();
-        g1_wait_pieces<0>();   // unit u + 1's weights (and, issued in front of them, the next channel stage's window)
+        sched_fence();
+        dma_wait<0>();   // unit u + 1's weights (and, issued in front of them, the next channel stage's window)
         lds_barrier();
         // the next unit and the one behind it
         int cs1 = cs, t1 = t + 1;
@@ -198,17 +198,17 @@ __global__ void __launch_bounds__(256) AICG_WAVES_PER_SIMD(WPS) conv_g1k_kernel(
         if (more) unit_rsrc(cs2, t2);
         const int sig1 = t1 * p.dw + delta0;
         read_a(a0, a_nxt, 0);
-        w2d_fence();
+        sched_fence();
         mma_group(sig & 3, a1, window_ptr(bbuf + (cs1 & 1) * BSTAGE, 0, sig1 >> 2), std::true_type{}, std::true_type{}, more, a_fill);
         float* tmp = a_cur; a_cur = a_nxt; a_nxt = a_fill; a_fill = tmp;
         cs = cs1; t = t1; sig = sig1;
     }
     {
-        w2d_fence();
+        sched_fence();
         read_a(a1, a_cur, 1);
-        w2d_fence();
+        sched_fence();
         mma_group(sig & 3, a0, window_ptr(bbuf + (cs & 1) * BSTAGE, 1, sig >> 2), std::true_type{}, std::false_type{}, false, nullptr);
-        w2d_fence();
+        sched_fence();
         mma_group(sig & 3, a1, nullptr, std::false_type{}, std::false_type{}, false, nullptr);
     }
     g1_epilogue<TM, false>(p, acc, img, m_base + wm * (TM * 32), n0 + wn * 128 + 4 * l31, T);

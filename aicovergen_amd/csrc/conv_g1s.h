@@ -93,9 +93,9 @@ __global__ void __launch_bounds__(256) AICG_WAVES_PER_SIMD(WPS) conv_g1s_kernel(
     };
     auto issue_piece = [&](int e, float* abuf, float* wbuf) __attribute__((always_inline)) {   // e < PA: weights, else window
         if (e < PA) {
-            if (4 * e + 3 < NA || wave + 4 * e < NA) w2d_dma16(wb, aoff[e], wsoff, abuf + (wave + 4 * e) * 256, lane);
+            if (4 * e + 3 < NA || wave + 4 * e < NA) dma16(wb, aoff[e], wsoff, abuf + (wave + 4 * e) * 256, lane);
         } else {
-            if (4 * (e - PA) + 3 < NB || wave + 4 * (e - PA) < NB) w2d_dma16(xb, boff[e - PA], 0u, wbuf + (wave + 4 * (e - PA)) * 256, lane);
+            if (4 * (e - PA) + 3 < NB || wave + 4 * (e - PA) < NB) dma16(xb, boff[e - PA], 0u, wbuf + (wave + 4 * (e - PA)) * 256, lane);
         }
     };
     auto issue = [&](int u, float* abuf, float* wbuf) __attribute__((always_inline)) {
@@ -148,19 +148,19 @@ __global__ void __launch_bounds__(256) AICG_WAVES_PER_SIMD(WPS) conv_g1s_kernel(
                 acc[i][3] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b3, acc[i][3], 0, 0, 0);
                 if constexpr (DMA) {
                     const int blk = s * TM + i;
-                    w2d_fence();
+                    sched_fence();
                     if (more) {
 #pragma unroll
                         for (int e = 0; e < PW; ++e)
                             if (e * NBLK / PW == blk) issue_piece(e, afill, wfill);
                     }
-                    w2d_fence();
+                    sched_fence();
                 }
             }
             if constexpr (RELOAD) {
-                w2d_fence();
+                sched_fence();
                 read_b_step(nxtw, s);
-                w2d_fence();
+                sched_fence();
             }
         }
     };
@@ -174,7 +174,7 @@ __global__ void __launch_bounds__(256) AICG_WAVES_PER_SIMD(WPS) conv_g1s_kernel(
     float* a_fill = smem + 2 * ASTAGE;
     issue(0, a_cur, bbuf);
     if (nu > 1) issue(1, a_nxt, bbuf + BSTAGE);
-    g1_wait_pieces<0>();
+    dma_wait<0>();
     lds_barrier();
     float4 a0[TM], a1[TM];
     read_a(a0, a_cur, 0);
@@ -183,41 +183,41 @@ __global__ void __launch_bounds__(256) AICG_WAVES_PER_SIMD(WPS) conv_g1s_kernel(
     for (int u = 0; u + 1 < nu; ++u) {
         float* const w_nxt = bbuf + ((u + 1) & 1) * BSTAGE;           // unit u + 1's window; unit u's buffer takes unit u + 2's
         float* const w_fill = bbuf + (u & 1) * BSTAGE;
-        w2d_fence();
+        sched_fence();
         read_a(a1, a_cur, 1);
-        w2d_fence();
+        sched_fence();
         mma_tap(Tag0{}, a0, std::false_type{}, nullptr, std::false_type{}, false, nullptr, nullptr);
-        w2d_fence();
-        g1_wait_pieces<0>();   // this wave's pieces of unit u + 1 (the only ones in flight)
+        sched_fence();
+        dma_wait<0>();   // this wave's pieces of unit u + 1 (the only ones in flight)
         lds_barrier();         // unit u + 1 is complete; every wave is done with unit u - 1 and holds unit u's window in registers
         const bool more = u + 2 < nu;
         if (more) unit_rsrc(u + 2);
         if constexpr (KT == 3) {
             read_a(a0, a_cur, 2);
-            w2d_fence();
+            sched_fence();
             mma_tap(Tag1{}, a1, std::false_type{}, nullptr, std::true_type{}, more, a_fill, w_fill);
-            w2d_fence();
+            sched_fence();
             read_a(a1, a_nxt, 0);
-            w2d_fence();
+            sched_fence();
             mma_tap(Tag2{}, a0, std::true_type{}, w_nxt, std::false_type{}, false, nullptr, nullptr);
 #pragma unroll
             for (int i = 0; i < TM; ++i) a0[i] = a1[i];
         } else {
             read_a(a0, a_nxt, 0);
-            w2d_fence();
+            sched_fence();
             mma_tap(Tag1{}, a1, std::true_type{}, w_nxt, std::true_type{}, more, a_fill, w_fill);
         }
         float* t = a_cur; a_cur = a_nxt; a_nxt = a_fill; a_fill = t;
     }
     {   // the last unit, peeled: nothing to publish, prefetch or reload
-        w2d_fence();
+        sched_fence();
         read_a(a1, a_cur, 1);
-        w2d_fence();
+        sched_fence();
         mma_tap(Tag0{}, a0, std::false_type{}, nullptr, std::false_type{}, false, nullptr, nullptr);
         if constexpr (KT == 3) {
-            w2d_fence();
+            sched_fence();
             read_a(a0, a_cur, 2);
-            w2d_fence();
+            sched_fence();
         }
         mma_tap(Tag1{}, a1, std::false_type{}, nullptr, std::false_type{}, false, nullptr, nullptr);
         if constexpr (KT == 3) mma_tap(Tag2{}, a0, std::false_type{}, nullptr, std::false_type{}, false, nullptr, nullptr);

@@ -148,14 +148,14 @@ __global__ void __launch_bounds__(256) AICG_WAVES_PER_SIMD(WPS) conv_g1w_kernel(
         const unsigned soff = (unsigned)(((long)sl0 * wslot_q + (long)kb * 2 * p.Mpad) * 16);
 #pragma unroll
         for (int e = 0; e < PA; ++e)
-            if (wave + 4 * e < npiece) w2d_dma16(wb, ao[e], soff, abuf + (wave + 4 * e) * 256, lane);
+            if (wave + 4 * e < npiece) dma16(wb, ao[e], soff, abuf + (wave + 4 * e) * 256, lane);
     };
     auto issue_b = [&](const unsigned (&bo)[PB], const float* xi, int cs, float* dst) __attribute__((always_inline)) {
         const long left = (long)(p.Cin_g - cs * PL::CS) * p.x_sc * 4;       // absent channels read 0
         const BufRsrc xb = make_buf(xi + (long)cs * PL::CS * p.x_sc, (unsigned)lmin(left, 0x7fffffffL));
 #pragma unroll
         for (int e = 0; e < PB; ++e)
-            if (4 * e + 3 < NB || wave + 4 * e < NB) w2d_dma16(xb, bo[e], 0u, dst + (wave + 4 * e) * 256, lane);
+            if (4 * e + 3 < NB || wave + 4 * e < NB) dma16(xb, bo[e], 0u, dst + (wave + 4 * e) * 256, lane);
     };
 
     f32x16 M[4][2];                                       // [accumulator set][pair tile]
@@ -266,7 +266,7 @@ __global__ void __launch_bounds__(256) AICG_WAVES_PER_SIMD(WPS) conv_g1w_kernel(
     issue_b(boff, ximg, 0, bbuf);
     issue_unit(aoff, 0, 0, a_cur);
     issue_unit(aoff, 1 / PL::NU, 1 % PL::NU, a_nxt);      // (NU >= 2: unit 1 exists)
-    g1_wait_pieces<0>();
+    dma_wait<0>();
     lds_barrier();
     float4 af[4], an[4];                                  // A fragments of the running unit / of the next one
     float Vc[2][4], Vn[2][4];                             // operands of the running k-step / of the next one
@@ -302,19 +302,19 @@ __global__ void __launch_bounds__(256) AICG_WAVES_PER_SIMD(WPS) conv_g1w_kernel(
             }
         };
         // k-steps 0 and 1
-        w2d_fence();
+        sched_fence();
         prep(GT{}, 1, wbuf, rb, Vn);
-        if constexpr (SCH == 0) w2d_fence();
+        if constexpr (SCH == 0) sched_fence();
         mma(GT{}, 0, af, Vc);
         interleave();
-        w2d_fence();
+        sched_fence();
         prep(GT{}, 2, wbuf, rb, Vc);
-        if constexpr (SCH == 0) w2d_fence();
+        if constexpr (SCH == 0) sched_fence();
         mma(GT{}, 1, af, Vn);
         interleave();
-        w2d_fence();
+        sched_fence();
         if constexpr (SYNC) {
-            g1_wait_pieces<0>();   // this wave's pieces of unit u + 1 (and, issued in front of them, the next stage's window)
+            dma_wait<0>();   // this wave's pieces of unit u + 1 (and, issued in front of them, the next stage's window)
             lds_barrier();         // unit u + 1 (and, behind a stage's last unit, the next window) is complete; unit u - 1's buffer is free
             if constexpr (V == 0) {
                 if (cs + 1 < nst) issue_b(boff, ximg, cs + 1, bbuf + (wpar ^ 1) * BSTAGE);
@@ -329,17 +329,17 @@ __global__ void __launch_bounds__(256) AICG_WAVES_PER_SIMD(WPS) conv_g1w_kernel(
             if constexpr (PREF) load_a(GNT{}, a_nxt, an);
         }
         // k-steps 2 and 3
-        w2d_fence();
+        sched_fence();
         prep(GT{}, 3, wbuf, rb, Vn);
-        if constexpr (SCH == 0) w2d_fence();
+        if constexpr (SCH == 0) sched_fence();
         mma(GT{}, 2, af, Vc);
         interleave();
-        w2d_fence();
+        sched_fence();
         if constexpr (PREF) prep(GNT{}, 0, wnxt, rbn, Vc);
-        if constexpr (SCH == 0) w2d_fence();
+        if constexpr (SCH == 0) sched_fence();
         mma(GT{}, 3, af, Vn);
         if constexpr (PREF) interleave();
-        w2d_fence();
+        sched_fence();
         if constexpr (PREF) {
 #pragma unroll
             for (int sl = 0; sl < 4; ++sl) af[sl] = an[sl];
@@ -385,9 +385,9 @@ __global__ void __launch_bounds__(256) AICG_WAVES_PER_SIMD(WPS) conv_g1w_kernel(
                 M[0][j] = mfma_f16_32x32x8(ah[0], Vh[j][0], M[0][j]); M[3][j] = mfma_f16_32x32x8(ah[1], Vh[j][1], M[3][j]);
             }
         }
-        w2d_fence();
+        sched_fence();
         if constexpr (SYNC) {
-            g1_wait_pieces<0>();
+            dma_wait<0>();
             lds_barrier();
             if constexpr (V == 0) {
                 if (cs + 1 < nst) issue_b(boff, ximg, cs + 1, bbuf + (wpar ^ 1) * BSTAGE);
@@ -399,7 +399,7 @@ __global__ void __launch_bounds__(256) AICG_WAVES_PER_SIMD(WPS) conv_g1w_kernel(
             }
             if constexpr (PREF) pack_unit(GNT{}, a_nxt, wnxt, rbn);
         }
-        w2d_fence();
+        sched_fence();
         float* t = a_cur; a_cur = a_nxt; a_nxt = a_fill; a_fill = t;
         if constexpr (V + 1 == PL::NU) wpar ^= 1;
     };

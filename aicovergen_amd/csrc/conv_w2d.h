@@ -18,7 +18,7 @@
 // image; wave w owns row pair w >> 1 and tile block w & 1 (column pairs 16 (w & 1) .. + 15).  NW = 8 (two waves per SIMD: one
 // wave's issue bubbles are the other's MFMA time; 192 AGPRs + 64 VGPRs each) or 4 (one per SIMD, any number of VGPRs, half the tile).
 // K runs in chunks of 8 input channels = 2 MFMA k-steps (lane group ks = lane >> 4 contracts channel 4 s + ks in step s).
-// One LDS stage per chunk, THREE buffers, filled by LDS DMA (buffer_load_dwordx4 ... lds: 1 KiB per wave-instruction, no staging
+// One LDS stage per chunk, THREE buffers, filled by LDS DMA (lds_dma.h; buffer_load_dwordx4 ... lds: 1 KiB per wave-instruction, no staging
 // registers, zero padding by the buffer range check) that the same waves issue two stages ahead:
 //     weights  [s][p][ks][m = 0..47]  floats: 24 KiB, a contiguous slab of the packed image
 //     patch    [channel c = 0..7][row 0..NW+1][18 quads] (+ pad quads: the plane stride is 8 mod 16 quads, which puts the four ks groups
@@ -33,11 +33,12 @@
 // Persistent walk over (tile, M unit) items, M unit fastest, XCD x owning a contiguous eighth of the list: the workgroups that
 // share an input patch run side by side on one L2.
 #pragma once
-#include "conv_kernels.h"
+#include <cstdint>
+
+#include "conv_args.h"
+#include "lds_dma.h"
 
 namespace aicg {
-
-typedef float w2d_f32x4 __attribute__((ext_vector_type(4)));
 
 static constexpr int kW2dM = 48;                                  // output channels per M unit
 static constexpr int kW2dCols = 64;                               // output columns of a workgroup's tile (its rows: NW)
@@ -48,108 +49,6 @@ static constexpr int kW2dWPieces = kW2dWFloats / 256;             // 24 DMA piec
 __host__ __device__ constexpr int w2d_plane_quads(int nw) { return ((nw + 2) * kW2dPQuads + 7) / 16 * 16 + 8; }
 __host__ __device__ constexpr int w2d_stage_floats(int nw) { return kW2dWFloats + 8 * w2d_plane_quads(nw) * 4; }
 
-// One LDS-DMA piece: lane l fetches 16 bytes at buffer offset voff (+ the wave-uniform soff) and the hardware writes them to
-// lds_wave_base + 16 l.  Offsets >= the resource's num_records (kBufOob) deposit zeros -- the convolution's padding.
-__device__ __forceinline__ void w2d_dma16(const BufRsrc& r, unsigned voff, unsigned soff, float* lds_wave_base, int lane) {
-#ifdef AICG_EMULATED
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if ((unsigned long)voff + 16 <= r.num_records) __builtin_memcpy(&v, r.base + voff + soff, 16);
-    *reinterpret_cast<float4*>(lds_wave_base + 4 * lane) = v;
-#else
-    (void)lane;
-    // inline asm on purpose (tdf_pair.hip): with the builtin hipcc guards every following ds_read with a vmcnt(0); the stage-end
-    // w2d_dma_wait() orders it by hand.  M0 = LDS base of the piece, restored.
-    const unsigned lds = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)lds_wave_base);
-    const unsigned so = __builtin_amdgcn_readfirstlane(soff);
-    buf_i32x4 rs;   // wave-uniform by construction; say so (a resource the compiler cannot prove uniform lands in VGPRs)
-    rs.x = __builtin_amdgcn_readfirstlane(r.d.x); rs.y = __builtin_amdgcn_readfirstlane(r.d.y);
-    rs.z = __builtin_amdgcn_readfirstlane(r.d.z); rs.w = __builtin_amdgcn_readfirstlane(r.d.w);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(voff), "s"(rs), "s"(lds), "s"(so)
-                 : "memory");
-#endif
-}
-// A RUN of N <= 4 pieces of one resource whose LDS destinations are consecutive KiB (piece e lands at lds_base + 1 KiB x e), issued as ONE
-// statement with one M0 save / restore (N calls of w2d_dma16 are 9 N instructions + a generic-to-LDS pointer cast with its null check
-// each; profiles/NOTES.md R6: the probe's L2-resident burst of 48 pieces lands at 44 B per clock and CU, while conv_w2d's waves stood
-// ~3 000 cycles per stage in ~150 issue slots of address arithmetic and three exposed LDS reads).
-//   SAME: a contiguous slab (the weights) -- every piece uses the per-lane offset v[0] and the wave-uniform `soff`; the instruction's
-//         12-bit immediate advances the memory AND the LDS address by 1 KiB x e (LDS_ADDR = M0 base + inst_offset + 16 x lane): N + 4
-//         instructions;
-//   else: piece e has its own per-lane offsets v[e] (the patch; kBufOob = padding) and M0 itself is advanced: 3 N + 2 instructions.
-template <int N, bool SAME>
-__device__ __forceinline__ void w2d_dma_run(const BufRsrc& r, const unsigned (&v)[4], unsigned soff, float* lds_base, unsigned lds_addr, int lane) {
-    static_assert(N >= 1 && N <= 4, "the immediate offset has 12 bits");
-#ifdef AICG_EMULATED
-    (void)lds_addr;
-#pragma unroll
-    for (int e = 0; e < N; ++e) {
-        const unsigned voff = SAME ? v[0] + 1024u * e : v[e];      // the hardware range-checks voff + the immediate (not the scalar offset)
-        float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
-        if ((unsigned long)voff + 16 <= r.num_records) __builtin_memcpy(&q, r.base + voff + soff, 16);
-        *reinterpret_cast<float4*>(lds_base + 256 * e + 4 * lane) = q;
-    }
-#else
-    (void)lane; (void)lds_base;
-    buf_i32x4 rs;
-    rs.x = __builtin_amdgcn_readfirstlane(r.d.x); rs.y = __builtin_amdgcn_readfirstlane(r.d.y);
-    rs.z = __builtin_amdgcn_readfirstlane(r.d.z); rs.w = __builtin_amdgcn_readfirstlane(r.d.w);
-    const unsigned lds = __builtin_amdgcn_readfirstlane(lds_addr);
-    const unsigned so = __builtin_amdgcn_readfirstlane(soff);
-    unsigned keep;
-#define W2D_HEAD "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-#define W2D_TAIL "s_mov_b32 m0, %0"
-#define W2D_BUMP "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\t"
-    if constexpr (SAME) {
-        if constexpr (N == 1)
-            asm volatile(W2D_HEAD "buffer_load_dwordx4 %4, %1, %3 offen lds\n\t" W2D_TAIL
-                         : "=&s"(keep) : "s"(rs), "s"(lds), "s"(so), "v"(v[0]) : "memory");
-        else if constexpr (N == 2)
-            asm volatile(W2D_HEAD "buffer_load_dwordx4 %4, %1, %3 offen lds\n\tbuffer_load_dwordx4 %4, %1, %3 offen offset:1024 lds\n\t" W2D_TAIL
-                         : "=&s"(keep) : "s"(rs), "s"(lds), "s"(so), "v"(v[0]) : "memory");
-        else if constexpr (N == 3)
-            asm volatile(W2D_HEAD "buffer_load_dwordx4 %4, %1, %3 offen lds\n\tbuffer_load_dwordx4 %4, %1, %3 offen offset:1024 lds\n\t"
-                         "buffer_load_dwordx4 %4, %1, %3 offen offset:2048 lds\n\t" W2D_TAIL
-                         : "=&s"(keep) : "s"(rs), "s"(lds), "s"(so), "v"(v[0]) : "memory");
-        else
-            asm volatile(W2D_HEAD "buffer_load_dwordx4 %4, %1, %3 offen lds\n\tbuffer_load_dwordx4 %4, %1, %3 offen offset:1024 lds\n\t"
-                         "buffer_load_dwordx4 %4, %1, %3 offen offset:2048 lds\n\tbuffer_load_dwordx4 %4, %1, %3 offen offset:3072 lds\n\t" W2D_TAIL
-                         : "=&s"(keep) : "s"(rs), "s"(lds), "s"(so), "v"(v[0]) : "memory");
-    } else {
-        if constexpr (N == 1)
-            asm volatile(W2D_HEAD "buffer_load_dwordx4 %4, %1, %3 offen lds\n\t" W2D_TAIL
-                         : "=&s"(keep) : "s"(rs), "s"(lds), "s"(so), "v"(v[0]) : "memory");
-        else if constexpr (N == 2)
-            asm volatile(W2D_HEAD "buffer_load_dwordx4 %4, %1, %3 offen lds\n\t" W2D_BUMP "buffer_load_dwordx4 %5, %1, %3 offen lds\n\t" W2D_TAIL
-                         : "=&s"(keep) : "s"(rs), "s"(lds), "s"(so), "v"(v[0]), "v"(v[1]) : "memory", "scc");
-        else if constexpr (N == 3)
-            asm volatile(W2D_HEAD "buffer_load_dwordx4 %4, %1, %3 offen lds\n\t" W2D_BUMP "buffer_load_dwordx4 %5, %1, %3 offen lds\n\t"
-                         W2D_BUMP "buffer_load_dwordx4 %6, %1, %3 offen lds\n\t" W2D_TAIL
-                         : "=&s"(keep) : "s"(rs), "s"(lds), "s"(so), "v"(v[0]), "v"(v[1]), "v"(v[2]) : "memory", "scc");
-        else
-            asm volatile(W2D_HEAD "buffer_load_dwordx4 %4, %1, %3 offen lds\n\t" W2D_BUMP "buffer_load_dwordx4 %5, %1, %3 offen lds\n\t"
-                         W2D_BUMP "buffer_load_dwordx4 %6, %1, %3 offen lds\n\t" W2D_BUMP "buffer_load_dwordx4 %7, %1, %3 offen lds\n\t" W2D_TAIL
-                         : "=&s"(keep) : "s"(rs), "s"(lds), "s"(so), "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]) : "memory", "scc");
-    }
-#undef W2D_HEAD
-#undef W2D_TAIL
-#undef W2D_BUMP
-#endif
-}
-template <bool SKIP = false>
-__device__ __forceinline__ void w2d_dma_wait() {
-    if constexpr (SKIP) return;                      // (ABL 32768: what the stage-end wait costs; races, wrong results)
-#ifndef AICG_EMULATED
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-}
-__device__ __forceinline__ void w2d_fence() {
-#ifndef AICG_EMULATED
-    __builtin_amdgcn_sched_barrier(0);
-#endif
-}
 // One MFMA of the k-step pipeline, accumulating IN PLACE.  TIED: inline asm whose "+v" operand pins the destination to the addend.  With
 // the builtin hipcc is free to give v_mfma a destination other than its addend, and in the straight-line k-steps around the steady loop
 // (an item's first stage behind its zero-started k-step, its whole last stage) it does -- it uses the MFMA to move accumulator quads into
@@ -158,7 +57,7 @@ __device__ __forceinline__ void w2d_fence() {
 // quad, a vmcnt(0) in front of the reload that also waits for the epilogue's stores).  The hazard recogniser does not see inside inline
 // asm: the only non-MFMA readers of an accumulator are the epilogue's VALU instructions, behind w2d_mfma_settle().
 template <bool TIED>
-__device__ __forceinline__ void w2d_mfma_acc(w2d_f32x4& c, float a, float b) {
+__device__ __forceinline__ void w2d_mfma_acc(f32x4& c, float a, float b) {
 #ifdef AICG_EMULATED
     c = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 #else
@@ -167,12 +66,12 @@ __device__ __forceinline__ void w2d_mfma_acc(w2d_f32x4& c, float a, float b) {
 #endif
 }
 template <bool TIED>
-__device__ __forceinline__ void w2d_mfma_zero(w2d_f32x4& c, float a, float b) {   // an item's first k-step: the addend is the inline constant 0
+__device__ __forceinline__ void w2d_mfma_zero(f32x4& c, float a, float b) {   // an item's first k-step: the addend is the inline constant 0
 #ifdef AICG_EMULATED
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, w2d_f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
 #else
     if constexpr (TIED) asm("v_mfma_f32_16x16x4_f32 %0, %1, %2, 0" : "=&v"(c) : "v"(a), "v"(b));
-    else c = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, w2d_f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+    else c = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
 #endif
 }
 // an 8-pass MFMA's result may be read by a VALU / VMEM instruction 11 wait states after it issued (hipcc inserts them for the builtin)
@@ -194,8 +93,9 @@ __device__ inline T w2d_opaque(T v) {   // a per-item copy of a uniform value th
 // fragments -- [s][p / 2][ks][m][p % 2], one ds_read_b64 per two MFMAs.
 // ABL: profiling variants, instantiated in the dev library only (tools/kbench_w2d_ablate.py): 1 no DMA, 2 no fragment reads, 4 no patch
 // reads / transform, 8 no MFMAs, 16 no epilogue, 32 no stage barriers, 64 clocks of workgroup 0 into y[0..1], 128 epilogue without its
-// stores, 8192 place() at the top of the stage that needs it, 512 the round-4 / 5 stage burst (one w2d_dma16 per piece, pieces w, w + NW, ... of the patch) for A/B against the runs of
-// w2d_dma_run.  Compile-time: a run-time switch in the k-step loop costs the 8-wave form its register budget.
+// stores, 8192 place() at the top of the stage that needs it, 512 the round-4 / 5 stage burst (one dma16 per piece, pieces w, w + NW, ...
+// of the patch) for A/B against the runs of dma_run.  Compile-time: a run-time switch in the k-step loop costs the 8-wave form its
+// register budget.
 // KS: k-steps per LDS stage.  2 (routed): stages of 8 input channels.  1 (development builds, aicg_conv_desc.wino 16): stages of 4 -- half
 // the weights slab (12 KiB) and four patch planes per stage, three stage buffers in < 64 KiB, so that TWO four-wave workgroups fit a CU
 // (each SIMD holds one wave of each) and what one workgroup cannot hide -- its barriers, its bursts, an item's epilogue and pipeline
@@ -269,7 +169,7 @@ __global__ void __launch_bounds__(64 * NW, KS == 1 ? 2 : 1) conv_w2d_kernel(Conv
     unsigned* const tab_s = reinterpret_cast<unsigned*>(bias_s + ((nmu * kW2dM + 3) & ~3));   // [2][NPP][NT]: decode, then offsets
 #pragma unroll
     for (int e = 0; e < NPP; ++e) {
-        const int piece = OLD_DMA ? wave + NW * e : wave * NPP + e;   // a wave's pieces are consecutive KiB of the stage: one run (w2d_dma_run)
+        const int piece = OLD_DMA ? wave + NW * e : wave * NPP + e;   // a wave's pieces are consecutive KiB of the stage: one run (dma_run)
         const int Q = piece * 64 + (tid & 63);
         const int c = Q / PLANEQ, rem = Q - c * PLANEQ;
         const int row = rem / kW2dPQuads, qd = rem - row * kW2dPQuads;
@@ -318,13 +218,13 @@ __global__ void __launch_bounds__(64 * NW, KS == 1 ? 2 : 1) conv_w2d_kernel(Conv
 #pragma unroll
             for (int e = 0; e < WPW; ++e) {
                 const int piece = wave * WPW + e;
-                w2d_dma16(wb, 16u * (unsigned)lane, 1024u * (unsigned)piece, buf + piece * 256, lane);
+                dma16(wb, 16u * (unsigned)lane, 1024u * (unsigned)piece, buf + piece * 256, lane);
             }
             const unsigned* tl = tab_s + NPP * NT + wave * 64 + lane;
 #pragma unroll
             for (int e = 0; e < NPP; ++e) {
                 const int piece = wave + NW * e;
-                if (piece < PPIECES) w2d_dma16(xb, tl[e * NT], 0u, buf + WFLOATS + piece * 256, lane);
+                if (piece < PPIECES) dma16(xb, tl[e * NT], 0u, buf + WFLOATS + piece * 256, lane);
             }
         } else {
             // the stage buffer's LDS byte address as scalar arithmetic on the workgroup's LDS base (no generic-to-LDS cast per piece)
@@ -336,27 +236,27 @@ __global__ void __launch_bounds__(64 * NW, KS == 1 ? 2 : 1) conv_w2d_kernel(Conv
             for (int e = 0; e < NPP; ++e) po[e] = tl[e * NT];
             const unsigned wv[4] = {16u * (unsigned)lane, 0u, 0u, 0u};
             static_assert(WPW == 3 || WPW == 6, "weight pieces per wave");
-            w2d_dma_run<3, true>(wb, wv, 1024u * (unsigned)(wave * WPW), buf + wave * WPW * 256, buf_lds + 1024u * (unsigned)(wave * WPW), lane);
+            dma_run<3, true>(wb, wv, 1024u * (unsigned)(wave * WPW), buf + wave * WPW * 256, buf_lds + 1024u * (unsigned)(wave * WPW), lane);
             if constexpr (WPW == 6)
-                w2d_dma_run<3, true>(wb, wv, 1024u * (unsigned)(wave * WPW + 3), buf + (wave * WPW + 3) * 256,
+                dma_run<3, true>(wb, wv, 1024u * (unsigned)(wave * WPW + 3), buf + (wave * WPW + 3) * 256,
                                      buf_lds + 1024u * (unsigned)(wave * WPW + 3), lane);
             // this wave's patch pieces wave NPP .. + NPP - 1 (the last wave may own fewer: PPIECES is not a multiple of NW)
             float* pdst = buf + WFLOATS + wave * NPP * 256;
             const unsigned pdst_lds = buf_lds + (unsigned)(WFLOATS * 4) + 1024u * (unsigned)(wave * NPP);
             const int mine_p = PPIECES - wave * NPP;          // >= NPP except on the last wave
             if constexpr ((dbg & 2048) != 0) { (void)pdst; (void)pdst_lds; (void)mine_p; }   // ABL 2048: weights only (wrong results)
-            else if (mine_p >= NPP) w2d_dma_run<NPP, false>(xb, po, 0u, pdst, pdst_lds, lane);
+            else if (mine_p >= NPP) dma_run<NPP, false>(xb, po, 0u, pdst, pdst_lds, lane);
             else {
                 constexpr int LASTN = PPIECES - (NW - 1) * NPP;   // 23 - 21 = 2 (eight waves), 15 - 12 = 3 (four)
                 static_assert(LASTN >= 1 && LASTN <= NPP, "the last wave owns at least one piece");
-                w2d_dma_run<LASTN, false>(xb, po, 0u, pdst, pdst_lds, lane);
+                dma_run<LASTN, false>(xb, po, 0u, pdst, pdst_lds, lane);
             }
         }
         if (++lc == nchunk) { lc = 0; ++li; }
     };
 
     // ---- the k-step pipeline's registers
-    w2d_f32x4 acc[16][3];
+    f32x4 acc[16][3];
     float V[16];                                     // B operands of the running k-step, per point
     float2 raw[4][3];                                // the next k-step's patch as loaded: [patch row][aligned column pair]
     float N[4][4];                                   // ... on its way to V: R = B^T d, then V = R B in place
@@ -448,7 +348,7 @@ __global__ void __launch_bounds__(64 * NW, KS == 1 ? 2 : 1) conv_w2d_kernel(Conv
 #pragma unroll
             for (int st = 0; st < NST; ++st) {
                 const int pg = st / 3, rb = st - 3 * pg;
-                w2d_fence();
+                sched_fence();
                 if constexpr ((dbg & 4) == 0 && PREP) {
                     if (st == 8 * SC) rows_to_R(0, 2);
                     else if (st == 9 * SC) rows_to_R(2, 4);
@@ -461,11 +361,11 @@ __global__ void __launch_bounds__(64 * NW, KS == 1 ? 2 : 1) conv_w2d_kernel(Conv
                     float av;
                     if constexpr (G == 4) av = p4 == 0 ? aq[rb].x : p4 == 1 ? aq[rb].y : p4 == 2 ? aq[rb].z : aq[rb].w;
                     else av = p4 == 0 ? ap[rb].x : ap[rb].y;
-                    if constexpr ((dbg & 8) != 0) { if constexpr (FIRST) acc[pt][rb] = w2d_f32x4{0.f, 0.f, 0.f, 0.f}; continue; }
+                    if constexpr ((dbg & 8) != 0) { if constexpr (FIRST) acc[pt][rb] = f32x4{0.f, 0.f, 0.f, 0.f}; continue; }
                     if constexpr (FIRST) w2d_mfma_zero<TIED>(acc[pt][rb], av, V[pt]);
                     else w2d_mfma_acc<TIED>(acc[pt][rb], av, V[pt]);
                 }
-                w2d_fence();
+                sched_fence();
                 if (pg < NG - 1) fetch_q(cur, s, pg + 1, rb);
                 else if constexpr (PREP) fetch_q(nxt, sn, 0, rb);
                 if constexpr ((dbg & 4) == 0 && PREP) {
@@ -483,7 +383,7 @@ __global__ void __launch_bounds__(64 * NW, KS == 1 ? 2 : 1) conv_w2d_kernel(Conv
             if constexpr ((dbg & 4) == 0 && PREP) {
                 if (pt == 8 || pt == 9) load_raw(nxt, sn, 2 * (pt - 8), 2 * (pt - 8) + 2);
             }
-            w2d_fence();
+            sched_fence();
             if constexpr ((dbg & 4) == 0 && PREP) {
                 if (pt >= 10 && pt < 14) rows_to_R(pt - 10, pt - 9);
                 else if (pt == 14) R_to_V(0, 2);
@@ -491,11 +391,11 @@ __global__ void __launch_bounds__(64 * NW, KS == 1 ? 2 : 1) conv_w2d_kernel(Conv
             }
 #pragma unroll
             for (int rb = 0; rb < 3; ++rb) {
-                if constexpr ((dbg & 8) != 0) { if constexpr (FIRST) acc[pt][rb] = w2d_f32x4{0.f, 0.f, 0.f, 0.f}; continue; }
+                if constexpr ((dbg & 8) != 0) { if constexpr (FIRST) acc[pt][rb] = f32x4{0.f, 0.f, 0.f, 0.f}; continue; }
                 if constexpr (FIRST) w2d_mfma_zero<TIED>(acc[pt][rb], ring[pt & PF][rb], V[pt]);
                 else w2d_mfma_acc<TIED>(acc[pt][rb], ring[pt & PF][rb], V[pt]);
             }
-            w2d_fence();
+            sched_fence();
         }
         if constexpr (PREP) take_V();
     };
@@ -518,7 +418,7 @@ __global__ void __launch_bounds__(64 * NW, KS == 1 ? 2 : 1) conv_w2d_kernel(Conv
     };
     issue(b_cur);
     issue(b_nxt);
-    w2d_dma_wait();
+    dma_wait();
     lds_barrier();                                   // the first stage(s) and the bias are in LDS
 #ifndef AICG_EMULATED
     long long clk0 = 0, wall0 = 0;
@@ -569,7 +469,7 @@ __global__ void __launch_bounds__(64 * NW, KS == 1 ? 2 : 1) conv_w2d_kernel(Conv
             if constexpr (FIRST) issue(b_fill);
             if constexpr (!FIRST && !LAST) place_ahead();
             stamp(std::integral_constant<int, 2>{});
-            w2d_dma_wait<(ABL & 32768) != 0>();
+            if constexpr ((ABL & 32768) == 0) dma_wait();   // (ABL 32768: what the stage-end wait costs; races, wrong results)
             stamp(std::integral_constant<int, 4>{});
             float* t1 = b_cur; b_cur = b_nxt; b_nxt = b_fill; b_fill = t1;
             return;
@@ -588,7 +488,7 @@ __global__ void __launch_bounds__(64 * NW, KS == 1 ? 2 : 1) conv_w2d_kernel(Conv
         if constexpr (LAST) kstep(std::false_type{}, std::false_type{}, b_cur, 1, b_nxt, 0);
         else kstep(std::false_type{}, std::true_type{}, b_cur, 1, b_nxt, 0);
         stamp(std::integral_constant<int, 3>{});
-        w2d_dma_wait<(ABL & 32768) != 0>();
+        if constexpr ((ABL & 32768) == 0) dma_wait();   // (ABL 32768: what the stage-end wait costs; races, wrong results)
         stamp(std::integral_constant<int, 4>{});
         float* t = b_cur; b_cur = b_nxt; b_nxt = b_fill; b_fill = t;
     };
@@ -617,7 +517,7 @@ __global__ void __launch_bounds__(64 * NW, KS == 1 ? 2 : 1) conv_w2d_kernel(Conv
             continue;
         }
         if constexpr (TIED) w2d_mfma_settle();
-        w2d_fence();   // the epilogue's index arithmetic stays out of the last k-step (scheduled into it, it pushed accumulators into scratch memory)
+        sched_fence();   // the epilogue's index arithmetic stays out of the last k-step (scheduled into it, it pushed accumulators into scratch memory)
         const int tw_i = tile % p.tiles_w, th_i = (tile / p.tiles_w) % p.tiles_h, n = tile / (p.tiles_w * p.tiles_h);
         const int ho = th_i * NW + 2 * (wave >> 1), wo = tw_i * kW2dCols + 2 * (16 * (wave & 1) + l15);
         const long y_sc = w2d_opaque(p.y_sc), y_sh = w2d_opaque(p.y_sh);
@@ -663,7 +563,7 @@ __global__ void __launch_bounds__(64 * NW, KS == 1 ? 2 : 1) conv_w2d_kernel(Conv
                     const float4 bq = *reinterpret_cast<const float4*>(brow + rb * 16);
 #pragma unroll
                     for (int rp = 0; rp < 4; rp += 2) {
-                        w2d_fence();   // one channel pair at a time (hoisted, the store addresses and their temporaries cost accumulator registers)
+                        sched_fence();   // one channel pair at a time (hoisted, the store addresses and their temporaries cost accumulator registers)
                         auto A = [&](int pt) __attribute__((always_inline)) { return w2d_f32x2{acc[pt][rb][rp], acc[pt][rb][rp + 1]}; };
                         const w2d_f32x2 b2 = rp == 0 ? w2d_f32x2{bq.x, bq.y} : w2d_f32x2{bq.z, bq.w};
                         // (a - b is v_pk_add_f32 with the negation as an operand modifier: there is no packed subtraction; rows of W = A^T M one
@@ -699,7 +599,7 @@ __global__ void __launch_bounds__(64 * NW, KS == 1 ? 2 : 1) conv_w2d_kernel(Conv
                 const float4 bq = *reinterpret_cast<const float4*>(brow + rb * 16);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    w2d_fence();   // one output channel at a time: hoisted, the twelve store addresses and their temporaries spill accumulators
+                    sched_fence();   // one output channel at a time: hoisted, the twelve store addresses and their temporaries spill accumulators
                     const int m = mu * kW2dM + rb * 16 + 4 * ks + r;
                     const float bm = r == 0 ? bq.x : r == 1 ? bq.y : r == 2 ? bq.z : bq.w;
                     float Wc[4][2];

@@ -25,6 +25,7 @@
 // the bias slice.  One stage = one 8-channel chunk = 12 taps.
 #pragma once
 #include "conv_kernels.h"
+#include "lds_dma.h"
 
 namespace aicg {
 
@@ -45,13 +46,6 @@ __device__ inline int per_tile_lane(int v) {   // the same for a per-lane value
 #endif
     return v;
 }
-__device__ __forceinline__ void sched_fence() {   // nothing moves across
-#ifndef AICG_EMULATED
-    __builtin_amdgcn_sched_barrier(0);
-#endif
-}
-
-typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 template <int BM, int ROWS>
 __global__ void __launch_bounds__(64 * ROWS + 256) conv_ws3w_kernel(ConvArgs p) {
@@ -313,7 +307,7 @@ __global__ void __launch_bounds__(64 * ROWS + 256) conv_ws3w_kernel(ConvArgs p) 
         // rb * 16 + 4 ks + r of the accumulator), pair blocks cb = 0..1 (pair cb * 16 + l15)
         const int ks = lane >> 4, l15 = lane & 15;
         const int par = ks & 1, e2 = ks >> 1;            // this slot's channels of a chunk: 2 (2 e2 + s) + par for k-step s = 0, 1
-        f32x4v acc[4][3][2];
+        f32x4 acc[4][3][2];
         for (int k = 0; k < my_tiles; ++k) {
             const int tile = first + slot + k * slots;
             const int tw_i = tile % p.tiles_w, th_i = (tile / p.tiles_w) % p.tiles_h, n = tile / (p.tiles_w * p.tiles_h);

@@ -15,8 +15,6 @@
 
 namespace aicg {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 struct GemmArgs {
     const float* a;
     const float* w;

@@ -19,13 +19,11 @@
 //            row-major W2 row per four steps.  One LDS stage = 32 output columns; its epilogue (bias, BatchNorm, ReLU,
 //            + x, float4 stores: a lane owns 4 consecutive f per register quad) runs behind H / 8 MFMAs.
 // x is read twice (phase 1 operand, phase 2 residual), out written once, nothing else touches HBM but the L2-resident weights.
-#include "common.h"
+#include "lds_dma.h"
 
 #include <cstdint>
 
 namespace aicg {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct TdfArgs {
     const float* x;
@@ -57,39 +55,9 @@ __host__ __device__ constexpr int tdf_stage_floats(int H) {
 
 // Staging (all 256 threads).  Stage st < n1: K-slab st of phase 1 (W1 quads + x quads); stage n1 + fb: W2 rows of output block fb.
 // Buffer st & 1.  The weight slabs are plain contiguous copies -- both images are laid out in HBM exactly as LDS wants them (W2 with
-// its row padding materialised) -- and go HBM -> LDS by DMA (global_load_lds_dwordx4: 1 KiB per wave-instruction, lane-linear
-// destination, no staging registers: the accumulators need them); only the x slab, whose 8 consecutive k per row are dealt to
-// two parity planes, passes through registers (four float4).
-__device__ __forceinline__ void lds_dma16(const float* g, float* lds_wave_base, int lane) {
-#ifdef AICG_EMULATED
-    *reinterpret_cast<float4*>(lds_wave_base + 4 * lane) = *reinterpret_cast<const float4*>(g);
-#else
-    (void)lane;
-    // Issued through inline asm ON PURPOSE.  With __builtin_amdgcn_global_load_lds the compiler knows the instruction writes LDS, cannot
-    // prove that the destination (the OTHER stage buffer) does not alias the fragment reads that follow, and puts an
-    // `s_waitcnt vmcnt(0)` in front of the first ds_read: every stage then exposes a full HBM round trip before its MFMAs (measured r3:
-    // 10.2 ms for the level-0 block, of which 3.9 ms remained with every MFMA removed).  The asm form is invisible to that pass; the
-    // hand-written dma_wait() at the end of the stage is what orders it.  M0 carries the wave-uniform LDS base and is restored.
-    const unsigned lds = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)lds_wave_base);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(g), "s"(lds)
-                 : "memory");
-#endif
-}
-__device__ __forceinline__ void sched_fence() {
-#ifndef AICG_EMULATED
-    __builtin_amdgcn_sched_barrier(0);
-#endif
-}
-// every DMA this wave issued has landed (the LDS-only barrier behind it publishes the stage)
-__device__ __forceinline__ void dma_wait() {
-#ifndef AICG_EMULATED
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-}
-
+// its row padding materialised) -- and go HBM -> LDS by DMA (lds_dma.h: lds_dma16 pieces of 1 KiB per wave-instruction, lane-linear
+// destination, no staging registers: the accumulators need them; dma_wait() at the end of a stage is what orders them); only the x
+// slab, whose 8 consecutive k per row are dealt to two parity planes, passes through registers (four float4).
 // n4 float4 (a multiple of 64) from src to dst, spread over the workgroup's four waves
 __device__ __forceinline__ void tdf_dma_slab(const float* src, float* dst, int n4, int tid) {
     const int lane = tid & 63, wave = tid >> 6;

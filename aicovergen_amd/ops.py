@@ -2,16 +2,16 @@
 functions validate shapes, allocate outputs with torch, and hand raw device pointers + the current HIP
 stream to libaicg_hip.so."""
 import contextlib
+import ctypes
 import functools
 import math
 import os
 import threading
+from collections import namedtuple
 
 import numpy as np
 import torch
-from . import _env
-
-from . import _lib
+from . import _env, _lib
 
 
 def _ptr(t):
@@ -60,6 +60,53 @@ def _call(name, *args):
 
 
 # ---------------------------------------------------------------------------------------------------
+# Optional per-stage accounting for bench.py's `stages` list (HIP events on the launch stream around the wrapped ops)
+# ---------------------------------------------------------------------------------------------------
+class StageProfile:
+    """name -> launches, algorithmic flops / bytes, HIP-event time.  Enabled with `ops.stage_profile = StageProfile()`."""
+
+    def __init__(self):
+        self.rec = {}
+
+    def add(self, name, e0, e1, flops, nbytes):
+        r = self.rec.setdefault(name, {"events": [], "flops": 0.0, "bytes": 0.0, "launches": 0})
+        r["events"].append((e0, e1))
+        r["flops"] += flops
+        r["bytes"] += nbytes
+        r["launches"] += 1
+
+    def summary(self):
+        torch.cuda.synchronize()
+        return {name: {"launches": r["launches"], "ms": sum(a.elapsed_time(b) for a, b in r["events"]), "flops": r["flops"], "bytes": r["bytes"]}
+                for name, r in self.rec.items()}
+
+
+stage_profile = None
+
+
+def _staged(name, work):
+    """Decorator: a call is one launch of stage `name`, timed only while a profile is set and the first argument is a CUDA tensor.  work(args, kwargs, result) -> (flops, HBM bytes)."""
+    def decorate(fn):
+        @functools.wraps(fn)
+        def wrapped(*a, **k):
+            prof = stage_profile
+            if prof is None or not (a and torch.is_tensor(a[0]) and a[0].is_cuda):
+                return fn(*a, **k)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            r = fn(*a, **k)
+            e1.record()
+            prof.add(name, e0, e1, *work(a, k, r))
+            return r
+        return wrapped
+    return decorate
+
+
+def _numel(*ts):
+    return float(sum(t.numel() for t in ts if t is not None))
+
+
+# ---------------------------------------------------------------------------------------------------
 # STFT / iSTFT
 # ---------------------------------------------------------------------------------------------------
 _fft_tables = {}
@@ -84,6 +131,7 @@ def fft_tables(n_fft, device, window=None):
     return window, tw_half, tw_full
 
 
+@_staged("stft", lambda a, k, r: (0.0, 4.0 * _numel(a[0], r)))
 def stft(x, n_fft, hop, n_bins_out=None, frame_major=False, window=None):
     """x: (n_sig, L) fp32.  Returns the complex spectrogram split into planes:
     frame_major=False -> (n_sig, 2, n_bins_out, n_frames)  [torch.stft + view_as_real + permute layout]
@@ -106,6 +154,7 @@ def stft(x, n_fft, hop, n_bins_out=None, frame_major=False, window=None):
     return out
 
 
+@_staged("istft", lambda a, k, r: (0.0, 4.0 * _numel(a[0], r)))
 def istft(spec, n_fft, hop, length, frame_major=False, window=None):
     """spec: (n_sig, 2, n_bins_in, n_frames) (or (n_sig, 2, n_frames, n_bins_in) if frame_major);
     bins above n_bins_in are zero.  Returns (n_sig, length)."""
@@ -132,22 +181,15 @@ def istft(spec, n_fft, hop, length, frame_major=False, window=None):
 # ---------------------------------------------------------------------------------------------------
 # Convolution (implicit GEMM on fp32 MFMA)
 # ---------------------------------------------------------------------------------------------------
-import ctypes
-
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_GELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2, 3, 4, 5
 
 
 class ConvDesc(ctypes.Structure):
     """Mirror of aicg_conv_desc (include/aicg.h)."""
-    _fields_ = [(n, ctypes.c_int32) for n in
-                ("N", "Cin", "H", "W", "Cout", "Ho", "Wo", "KH", "KW", "stride_h", "stride_w", "pad_h", "pad_w",
-                 "dil_h", "dil_w", "groups")] + \
-               [(n, ctypes.c_int64) for n in ("x_sn", "x_sc", "x_sh", "y_sn", "y_sc", "y_sh", "r_sn", "r_sc", "r_sh")] + \
-               [("pre_act", ctypes.c_int32), ("pre_slope", ctypes.c_float), ("act", ctypes.c_int32),
-                ("act_slope", ctypes.c_float), ("out_scale", ctypes.c_float), ("accumulate", ctypes.c_int32),
-                ("res_before_act", ctypes.c_int32), ("pad_h_end", ctypes.c_int32), ("pad_w_end", ctypes.c_int32),
-                ("shuffle", ctypes.c_int32), ("res_mul", ctypes.c_int32), ("packed_v3", ctypes.c_int32),
-                ("split", ctypes.c_int32), ("wino", ctypes.c_int32), ("gemm_tile", ctypes.c_int32)]
+    _fields_ = [(n, ctypes.c_int32) for n in "N Cin H W Cout Ho Wo KH KW stride_h stride_w pad_h pad_w dil_h dil_w groups".split()] + \
+               [(n, ctypes.c_int64) for n in "x_sn x_sc x_sh y_sn y_sc y_sh r_sn r_sc r_sh".split()] + \
+               [(n, ctypes.c_float if n in ("pre_slope", "act_slope", "out_scale") else ctypes.c_int32) for n in
+                "pre_act pre_slope act act_slope out_scale accumulate res_before_act pad_h_end pad_w_end shuffle res_mul packed_v3 split wino gemm_tile".split()]
 
 
 def conv_bkc(taps):
@@ -246,8 +288,8 @@ def pack_conv_weight(w, groups=1, split=False):
 
 
 # Winograd F(2, 3) along rows for plain 3 x 3 layers (csrc/conv_ws3w.h): 12 instead of 18 MFMA contractions per output pair.  Layers
-# packed while this is set carry the transformed kernel next to the direct one; conv() takes it for large maps with a bias + none /
-# ReLU epilogue.  The f0 models (packed under fp32_layers()) never do: their goldens pin the direct summation order's bins.
+# packed while this is set carry the transformed kernel next to the direct one; conv() takes it where _winograd_applies.
+# The f0 models (packed under fp32_layers()) never do: their goldens pin the direct summation order's bins.
 winograd = _env.dev("AICG_WINOGRAD", "1") != "0"
 winograd_min_positions = 32768   # below this the 64-column tiles (4 or 8 rows) do not fill the chip (tests lower it)
 
@@ -258,12 +300,20 @@ def winograd_kernel(w):
     return torch.stack([g0, (g0 + g1 + g2) * 0.5, (g0 - g1 + g2) * 0.5, g2], -1).contiguous()
 
 
+def _aligned16(t4):   # 16-byte base address, batch and channel strides multiples of four floats
+    sn, sc = t4.stride()[:2]
+    return t4.data_ptr() % 16 == 0 and sn % 4 == 0 and sc % 4 == 0
+
+
+def _winograd_applies(pc, r4, wo, positions, is1d, pre_act, act, out_scale, accumulate, shuffle, out_len):   # bias + none / ReLU epilogue, even rows, enough output
+    return (pc.w_wino is not None and not is1d and r4 is None and not accumulate and pre_act == ACT_NONE and out_scale == 1.0
+            and act in (ACT_NONE, ACT_RELU) and not shuffle and out_len is None and wo % 2 == 0 and positions >= winograd_min_positions)
+
+
 # The two-dimensional form F(2 x 2, 3 x 3) (csrc/conv_w2d.h): 16 instead of 36 contractions per 2 x 2 output block, for layers whose
 # output channels come in units of 48 (every MDX-Net level).  AICG_WINOGRAD=1 keeps the row-only form everywhere.
 winograd2d = _env.dev("AICG_WINOGRAD", "2") == "2"
 winograd2d_waves = int(_env.dev("AICG_W2D_WAVES", "8"))   # 8: two waves per SIMD on an 8 x 64 tile; 4: one per SIMD on 4 x 64
-
-
 winograd2d_code = int(_env.dev("AICG_W2D_CODE", "0"))       # tools: a schedule variant under test (aicg_conv_desc.wino 6 ..)
 winograd2d_quads = _env.dev("AICG_W2D_QUADS", "0") == "1"   # fragment image: [s][p / 4][ks][m][p % 4] (16-byte fragments)
 # the eight-wave form reads PAIR fragments ([s][p / 2][ks][m][p % 2], one ds_read_b64 per two MFMAs: aicg_conv_desc.wino 12) unless
@@ -296,9 +346,13 @@ def winograd2d_image(w, quads=False, pairs=False):
     return Up.view(co // 48, 48, cpad // 8, 2, 4, 16).permute(0, 2, 3, 5, 4, 1).contiguous().view(-1)
 
 
+def _winograd2d_applies(pc, x4, w):   # a call on the row form takes the two-dimensional one: the layer has it, the map is float4-aligned
+    return winograd2d and pc.w_wino2 is not None and w % 4 == 0 and _aligned16(x4) and x4.stride(2) % 4 == 0
+
+
 # One-dimensional Winograd F(2, 3) for the vocoder's k = 3 / 7 / 11 ResBlock layers, dilation 1 / 3 / 5 (csrc/conv_g1w.h): 4 / 10 / 15 products
 # per output pair and input channel instead of 6 / 14 / 22.  Layers packed while this is set carry the slot image next to the direct one;
-# conv() takes it where the kernel applies (aligned rows, W % 4 == 0, enough positions).  The f0 models never do (fp32_layers()).
+# conv() takes it where _winograd1d_applies.  The f0 models never do (fp32_layers()).
 winograd1d = _env.dev("AICG_WINOGRAD1D", "1") != "0"
 winograd1d_min_positions = int(_env.dev("AICG_WINOGRAD1D_MIN", "16384"))
 
@@ -323,6 +377,18 @@ def winograd1d_kernel(w):
     return torch.stack(slots, -1).to(torch.float32).contiguous()
 
 
+def _winograd1d_applies(pc, x4, o4, r4, w, positions, is1d, pre_act, pre_slope, shuffle, res_mul, out_len):
+    """The first line is ours alone: the switch, 16 output channels and more (fewer -- the vocoder's conv_post, 32 -> 1 -- are one HBM pass: the
+    streaming kernels keep them), enough positions.  The rest is the other half of a contract with conv_g1w_applicable() (csrc/conv_g1w.h), in the
+    order of its clauses (its layer clauses are what packs w_wino1): a call sent there that the library rejects is an error, not a fall-through."""
+    return (winograd1d and pc.w_wino1 is not None and pc.cout >= 16 and positions >= winograd1d_min_positions
+            and is1d and out_len is None and w % 4 == 0
+            and pre_act in (ACT_NONE, ACT_LRELU) and 0.0 <= pre_slope <= 1.0
+            and not shuffle and not res_mul and w < (1 << 24) and x4.stride(1) < (1 << 24) and x4.stride(1) >= w
+            and _aligned16(x4) and _aligned16(o4) and (r4 is None or _aligned16(r4))
+            and 15 * (-(-(pc.cin // pc.groups) // 32) * 32) * (-(-pc.cout // 32) * 32) * 4 < (1 << 31))
+
+
 class PackedConv:
     """A convolution layer ready for aicg_conv_forward: packed weights + geometry.  1-D layers use KH=1."""
 
@@ -337,64 +403,57 @@ class PackedConv:
         else:
             stride, padding, dilation = _pair(stride), _pair(padding), _pair(dilation)
         self.cout, cin_g, self.kh, self.kw = weight.shape
-        self.cin = cin_g * groups
-        self.groups = groups
+        self.cin, self.groups = cin_g * groups, groups
         self.stride, self.padding, self.dilation = stride, padding, dilation
         device = weight.device if device is None else device
         self.split = bool(split_precision)
         self.fp32_only = _fp32_depth > 0                    # packed inside fp32_layers(): never marked for fp16 operands
         self.f16 = False                                    # mark_half()
-        self.w = pack_conv_weight(weight.to(device), groups, self.split)
+        w32 = weight.detach().to(device=device, dtype=torch.float32)    # the one fp32 device copy the packers share
+        self.w = pack_conv_weight(w32, groups, self.split)
         self.bias = None if bias is None else bias.detach().to(device=device, dtype=torch.float32).contiguous()
         self.w_wino = self.w_wino2 = self.w_wino1 = None
-        if (winograd1d and not self.split and not _fp32_depth and self.kh == 1 and self.kw in (3, 5, 7, 11) and stride == (1, 1)
-                and dilation[1] in ((1, 3, 5) if self.kw != 5 else (1,)) and padding == (0, (self.kw - 1) // 2 * dilation[1]) and self.padding_end is None
-                and groups == 1 and cin_g >= 16):
-            # slot image of the 1-D Winograd form, packed like any k-tap kernel (slots in the taps' place)
-            self.w_wino1 = pack_conv_weight(winograd1d_kernel(weight.detach().to(device=device, dtype=torch.float32)[:, :, 0]).unsqueeze(2), 1, False)
-        if (winograd and not self.split and not _fp32_depth and (self.kh, self.kw) == (3, 3) and stride == (1, 1) and dilation == (1, 1)
+        same_1d = (self.kh == 1 and self.kw in (3, 5, 7, 11) and stride == (1, 1) and padding == (0, (self.kw - 1) // 2 * dilation[1])
+                   and self.padding_end is None and groups == 1)     # odd-k same-padded stride-1 one-group 1-D: the 1-D Winograd form, conv_h
+        self._half = same_1d and not self.split and not self.fp32_only
+        # images built on first use, by kind ("dword" / "pairs" / "quads": wino2_image, "half": conv_h_image), from the caller's own tensor (a reference, normally host memory)
+        self._lazy_src, self._lazy_dev, self._lazy = weight.detach() if self._half else None, device, {}
+        routed = not self.split and not _fp32_depth   # the Winograd forms: never for split-precision or fp32_layers() layers
+        if winograd1d and routed and same_1d and dilation[1] in ((1, 3, 5) if self.kw != 5 else (1,)) and cin_g >= 16:
+            # slot image of the 1-D Winograd form, packed like any k-tap kernel (slots in the taps' place): the matrix pipe is given 4 / 7 / 10 / 15
+            # slots per output PAIR, not 2 k -- times 32 / 30 for the dilated layers' two idle lanes per tile
+            self.w_wino1 = pack_conv_weight(winograd1d_kernel(w32[:, :, 0]).unsqueeze(2), 1, False)
+            self._wino1_executed = {3: 4, 5: 7, 7: 10, 11: 15}[self.kw] / (2.0 * self.kw) * (1.0 if dilation[1] == 1 else 32.0 / 30.0)
+        if (winograd and routed and (self.kh, self.kw) == (3, 3) and stride == (1, 1) and dilation == (1, 1)
                 and padding == (1, 1) and self.padding_end is None and groups == 1 and cin_g >= 8):
-            self.w_wino = pack_conv_weight(winograd_kernel(weight.detach().to(device=device, dtype=torch.float32)), 1, False)
+            self.w_wino = pack_conv_weight(winograd_kernel(w32), 1, False)
             if winograd2d and self.cout % 48 == 0:
-                # ONE image on the device: the one the routed kernel reads (_w2d_code()).  The other fragment layouts (16/9 of the weights
-                # in HBM each) exist only for the dev switches / A-B tools: built on first use from the caller's own weight tensor (a
-                # reference, normally host memory), never for the product's layers
-                self._wino2_src, self._wino2_dev, self._wino2_images = weight.detach(), device, {}
+                # ONE image on the device, the one the routed kernel reads (_w2d_code()); the other layouts (16/9 of the weights each) are for the dev switches / A-B tools
+                self._lazy_src = weight.detach()
                 self.w_wino2 = self.wino2_image(_w2d_code()[1])
-
-        # half-storage kernel (conv_h): its fp16 image is built on first use from the caller's own weight tensor (a reference, normally
-        # host memory) -- a layer that never takes that route carries nothing
-        self._h_src, self._h_dev, self._h_image = None, device, None
-        if (not self.split and not self.fp32_only and self.kh == 1 and self.kw in (3, 5, 7, 11) and groups == 1 and stride == (1, 1) and self.padding_end is None
-                and padding == (0, (self.kw - 1) // 2 * dilation[1])):
-            self._h_src = weight.detach()
 
     def conv_h_supported(self):
         """This layer has a half-storage form (aicg_conv1d_h_supported; never for fp32_only or split-precision layers)."""
-        return self._h_src is not None and bool(_lib.get().aicg_conv1d_h_supported(self.cin, self.cout, self.kw, self.dilation[1]))
+        return self._half and bool(_lib.get().aicg_conv1d_h_supported(self.cin, self.cout, self.kw, self.dilation[1]))
 
     def conv_h_image(self):
         """aicg_conv1d_h's w_packed: fp16 (round to nearest even) [Cout_pad / 32][Cin / 8][k][2][32][4], built on first use."""
-        if self._h_image is None:
+        if "half" not in self._lazy:
             assert self.conv_h_supported(), "conv_h: layer has no half-storage form"
-            w = self._h_src.to(device=self._h_dev, dtype=torch.float32)[:, :, 0]
+            w = self._lazy_src.to(device=self._lazy_dev, dtype=torch.float32)[:, :, 0]
             cout, cin, k = w.shape
             cpad = 32 if cout <= 32 else -(-cout // 64) * 64
             wp = torch.zeros(cpad, cin, k, dtype=torch.float32, device=w.device)
             wp[:cout] = w
             # (m, i, g, h, e, tap) -> (m, g, tap, h, i, e)
-            self._h_image = wp.reshape(cpad // 32, 32, cin // 8, 2, 4, k).permute(0, 2, 5, 3, 1, 4).contiguous().half()
-        return self._h_image
+            self._lazy["half"] = wp.reshape(cpad // 32, 32, cin // 8, 2, 4, k).permute(0, 2, 5, 3, 1, 4).contiguous().half()
+        return self._lazy["half"]
 
     def wino2_image(self, kind):
         """The F(2 x 2, 3 x 3) weight image with "dword" / "pairs" / "quads" fragments (winograd2d_image)."""
-        if kind not in self._wino2_images:
-            self._wino2_images[kind] = winograd2d_image(self._wino2_src.to(device=self._wino2_dev, dtype=torch.float32),
-                                                         quads=kind == "quads", pairs=kind == "pairs")
-        return self._wino2_images[kind]
-
-    def wino2q(self):
-        return self.wino2_image("quads")
+        if kind not in self._lazy:
+            self._lazy[kind] = winograd2d_image(self._lazy_src.to(device=self._lazy_dev, dtype=torch.float32), quads=kind == "quads", pairs=kind == "pairs")
+        return self._lazy[kind]
 
     def out_hw(self, h, w):
         pe = self.padding if self.padding_end is None else self.padding_end
@@ -427,6 +486,20 @@ class ConvProfile:
         self.launches = 0
         self.shapes = []  # per launch: (shape key, flops) -- by_shape() groups them
 
+    def record(self, e0, e1, pc, x4, ho, wo, residual, accumulate, shuffle, form):
+        """One launch of conv(): its event pair, the layer, the input view, the map computed, the epilogue's reads, the form taken."""
+        n, c, h, w = x4.shape
+        weights = pc.cout * (pc.cin // pc.groups) * pc.kh * pc.kw
+        flops = 2.0 * n * weights * ho * wo
+        self.events.append((e0, e1))
+        self.flops += flops
+        self.flops_executed += flops * form.executed
+        self.bytes += 4.0 * (n * c * h * w + weights + n * pc.cout * ho * wo * (1 + bool(residual) + bool(accumulate)))
+        self.launches += 1
+        self.shapes.append(("N%d C%d>%d %dx%d k%dx%d s%d,%d d%d,%d g%d%s%s%s" % (
+            n, c, pc.cout, h, w, pc.kh, pc.kw, pc.stride[0], pc.stride[1], pc.dilation[0], pc.dilation[1], pc.groups,
+            " res" if residual else "", " acc" if accumulate else "", (" shuf" if shuffle else "") + form.label), flops))
+
     def by_shape(self):
         """[{shape, launches, ms, tflops, gflop}] sorted by time: where the family's time goes (bench.py --conv-shapes)."""
         torch.cuda.synchronize()
@@ -449,9 +522,36 @@ class ConvProfile:
 
 
 conv_profile = None
+gemm_tile = 0   # tools: aicg_conv_desc.gemm_tile of every launch (0 = the library's policy; 1 keeps 1 x 1 layers off csrc/conv_g1.h; 2 / 3 / 4 force a tile)
+# the form of one conv() call: aicg_conv_desc.wino, the image that code reads, the share of the direct form's multiply-adds executed, the shape key's suffix
+_ConvForm = namedtuple("_ConvForm", "wino image executed label")
 
-# tools: aicg_conv_desc.gemm_tile of every launch (0 = the library's policy; 1 keeps 1 x 1 layers off csrc/conv_g1.h; 2 / 3 / 4 force a tile)
-gemm_tile = 0
+
+def _conv_form(pc, x4, o4, r4, w, wo, positions, gate_positions, is1d, pre_act, pre_slope, act, out_scale, accumulate, shuffle, res_mul, out_len):
+    if _winograd_applies(pc, r4, wo, positions, is1d, pre_act, act, out_scale, accumulate, shuffle, out_len):
+        if _winograd2d_applies(pc, x4, w):
+            code, kind = _w2d_code()
+            return _ConvForm(code, pc.wino2_image(kind), 4.0 / 9.0, " wino2")    # F(2 x 2, 3 x 3): 16 of 36 multiply-adds
+        return _ConvForm(1, pc.w_wino, 2.0 / 3.0, " wino")                       # the row form: 12 of 18
+    if _winograd1d_applies(pc, x4, o4, r4, w, gate_positions, is1d, pre_act, pre_slope, shuffle, res_mul, out_len):
+        return _ConvForm(8, pc.w_wino1, pc._wino1_executed, " wino1d")
+    return _ConvForm(0, pc.w, 1.0, "")
+
+
+def _conv_desc(pc, x4, o4, r4, ho, wo, pre_act, pre_slope, act, act_slope, out_scale, accumulate, res_before_act, shuffle, res_mul, wino):
+    d = ConvDesc()
+    d.N, d.Cin, d.H, d.W = x4.shape
+    d.Cout, d.Ho, d.Wo, d.KH, d.KW, d.groups = pc.cout, ho, wo, pc.kh, pc.kw, pc.groups
+    (d.stride_h, d.stride_w), (d.pad_h, d.pad_w), (d.dil_h, d.dil_w) = pc.stride, pc.padding, pc.dilation
+    d.x_sn, d.x_sc, d.x_sh, _ = x4.stride()
+    d.y_sn, d.y_sc, d.y_sh, _ = o4.stride()
+    if r4 is not None:
+        d.r_sn, d.r_sc, d.r_sh, _ = r4.stride()
+    d.pre_act, d.pre_slope, d.act, d.act_slope, d.out_scale = pre_act, pre_slope, act, act_slope, out_scale
+    d.accumulate, d.res_before_act, d.res_mul = 1 if accumulate else 0, 1 if res_before_act else 0, 1 if res_mul else 0
+    d.pad_h_end, d.pad_w_end = (-1, -1) if pc.padding_end is None else pc.padding_end
+    d.shuffle, d.packed_v3, d.split, d.wino, d.gemm_tile = int(shuffle), 1, 1 if pc.split else 2 if pc.f16 else 0, wino, gemm_tile
+    return d
 
 
 def conv(x, pc, res=None, out=None, pre_act=ACT_NONE, pre_slope=0.0, act=ACT_NONE, act_slope=0.0, out_scale=1.0,
@@ -482,78 +582,26 @@ def conv(x, pc, res=None, out=None, pre_act=ACT_NONE, pre_slope=0.0, act=ACT_NON
     o4 = _as4d(out)
     assert o4.shape == oshape, (o4.shape, oshape)
     assert o4.stride(3) == 1 or wo == 1
-    r4 = None
-    if res is not None:
-        r4 = _as4d(res)
-        assert r4.shape == o4.shape and (r4.stride(3) == 1 or wo == 1)
+    r4 = None if res is None else _as4d(res)
+    assert r4 is None or (r4.shape == o4.shape and (r4.stride(3) == 1 or wo == 1))
     b = pc.bias if bias is None else bias
     if o4.numel() == 0:  # empty batch / no output positions: nothing to launch (empty tensors have no storage to point at)
         return out
     _check(x, out, res, pc.w, b)
-    d = ConvDesc()
-    d.N, d.Cin, d.H, d.W, d.Cout, d.Ho, d.Wo = n, c, h, w, pc.cout, ho, wo
-    d.KH, d.KW = pc.kh, pc.kw
-    d.stride_h, d.stride_w = pc.stride
-    d.pad_h, d.pad_w = pc.padding
-    d.dil_h, d.dil_w = pc.dilation
-    d.groups = pc.groups
-    d.x_sn, d.x_sc, d.x_sh = x4.stride(0), x4.stride(1), x4.stride(2)
-    d.y_sn, d.y_sc, d.y_sh = o4.stride(0), o4.stride(1), o4.stride(2)
-    if r4 is not None:
-        d.r_sn, d.r_sc, d.r_sh = r4.stride(0), r4.stride(1), r4.stride(2)
-    d.pre_act, d.pre_slope, d.act, d.act_slope = pre_act, pre_slope, act, act_slope
-    d.out_scale, d.accumulate = out_scale, 1 if accumulate else 0
-    d.res_before_act = 1 if res_before_act else 0
-    d.pad_h_end, d.pad_w_end = (-1, -1) if pc.padding_end is None else pc.padding_end
-    d.shuffle, d.res_mul = int(shuffle), 1 if res_mul else 0
-    d.packed_v3 = 1
-    d.split = 1 if getattr(pc, "split", False) else 2 if getattr(pc, "f16", False) else 0
-    # Winograd form: plain 3 x 3 layer, bias + none / ReLU epilogue, an even row length and enough output to fill the chip
-    wino = (getattr(pc, "w_wino", None) is not None and not is1d and res is None and not accumulate and pre_act == ACT_NONE
-            and out_scale == 1.0 and act in (ACT_NONE, ACT_RELU) and not shuffle and out_len is None and wo % 2 == 0
-            and n * ho * wo >= winograd_min_positions)
-    # ... its two-dimensional form where the layer has it and the map is float4-aligned
-    wino2 = (wino and winograd2d and getattr(pc, "w_wino2", None) is not None and w % 4 == 0 and x4.stride(0) % 4 == 0 and x4.stride(1) % 4 == 0
-             and x4.stride(2) % 4 == 0 and x4.data_ptr() % 16 == 0)
-    # the one-dimensional form F(2, 3) of a k = 3 / 7 / 11 layer (csrc/conv_g1w.h): aligned rows of a multiple of four positions
-    # (layers of fewer than 16 output channels -- the vocoder's conv_post, 32 -> 1 -- are one HBM pass: the streaming kernels keep them)
-    wino1 = (winograd1d and getattr(pc, "w_wino1", None) is not None and pc.cout >= 16 and is1d and not shuffle and out_len is None and w % 4 == 0
-             and n * gate_w >= winograd1d_min_positions and pre_act in (ACT_NONE, ACT_LRELU) and 0.0 <= pre_slope <= 1.0
-             and not res_mul and w < (1 << 24) and x4.stride(1) < (1 << 24)      # what csrc/conv_g1w.h's conv_g1w_applicable() also demands
-             and 15 * (-(-(c // pc.groups) // 32) * 32) * (-(-pc.cout // 32) * 32) * 4 < (1 << 31)
-             and x4.data_ptr() % 16 == 0 and x4.stride(0) % 4 == 0 and x4.stride(1) % 4 == 0 and x4.stride(1) >= w
-             and o4.data_ptr() % 16 == 0 and o4.stride(0) % 4 == 0 and o4.stride(1) % 4 == 0
-             and (r4 is None or (r4.data_ptr() % 16 == 0 and r4.stride(0) % 4 == 0 and r4.stride(1) % 4 == 0)))
-    # 2 / 3: eight / four waves per workgroup; + 2: quad fragments
-    d.gemm_tile = gemm_tile
-    w2code, w2kind = _w2d_code()
-    d.wino = w2code if wino2 else 1 if wino else 8 if wino1 else 0
+    form = _conv_form(pc, x4, o4, r4, w, wo, n * ho * wo, n * gate_w, is1d, pre_act, pre_slope, act, out_scale, accumulate, shuffle, res_mul, out_len)
+    d = _conv_desc(pc, x4, o4, r4, ho, wo, pre_act, pre_slope, act, act_slope, out_scale, accumulate, res_before_act, shuffle, res_mul, form.wino)
     prof = conv_profile
-    if prof is not None and x.is_cuda:
+    timed = prof is not None and x.is_cuda
+    if timed:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-    w_image = pc.wino2_image(w2kind) if wino2 else pc.w_wino if wino else pc.w_wino1 if wino1 else pc.w
     if plan_w is None:
-        _call("aicg_conv_forward", ctypes.addressof(d), _ptr(x4), _ptr(w_image), _ptr(b), _ptr(r4), _ptr(o4), _stream(x))
+        _call("aicg_conv_forward", ctypes.addressof(d), _ptr(x4), _ptr(form.image), _ptr(b), _ptr(r4), _ptr(o4), _stream(x))
     else:
-        _call("aicg_conv_forward_planned", ctypes.addressof(d), _ptr(x4), _ptr(w_image), _ptr(b), _ptr(r4), _ptr(o4), gate_w, _stream(x))
-    if prof is not None and x.is_cuda:
+        _call("aicg_conv_forward_planned", ctypes.addressof(d), _ptr(x4), _ptr(form.image), _ptr(b), _ptr(r4), _ptr(o4), gate_w, _stream(x))
+    if timed:
         e1.record()
-        prof.events.append((e0, e1))
-        prof.flops += 2.0 * n * pc.cout * (pc.cin // pc.groups) * pc.kh * pc.kw * ho * wo
-        # what the matrix pipe is given: F(2 x 2, 3 x 3) 16 of 36 multiply-adds, the row form 12 of 18, the 1-D form 4 / 7 / 10 / 15 slots per
-        # output PAIR where the direct form spends 2 k (k = 3 / 5 / 7 / 11) -- times 32 / 30 for the dilated layers' two idle lanes per tile
-        exe = 4.0 / 9.0 if wino2 else 2.0 / 3.0 if wino else 1.0
-        if wino1:
-            exe = {3: 4, 5: 7, 7: 10, 11: 15}[pc.kw] / (2.0 * pc.kw) * (1.0 if pc.dilation[1] == 1 else 32.0 / 30.0)
-        prof.flops_executed += 2.0 * n * pc.cout * (pc.cin // pc.groups) * pc.kh * pc.kw * ho * wo * exe
-        prof.bytes += 4.0 * (n * c * h * w + pc.cout * (pc.cin // pc.groups) * pc.kh * pc.kw
-                             + n * pc.cout * ho * wo * (1 + (r4 is not None) + bool(accumulate)))
-        prof.launches += 1
-        prof.shapes.append(("N%d C%d>%d %dx%d k%dx%d s%d,%d d%d,%d g%d%s%s%s" % (
-            n, c, pc.cout, h, w, pc.kh, pc.kw, pc.stride[0], pc.stride[1], pc.dilation[0], pc.dilation[1], pc.groups,
-            " res" if r4 is not None else "", " acc" if accumulate else "", (" shuf" if shuffle else "") + (" wino2" if wino2 else " wino" if wino else " wino1d" if wino1 else "")),
-            2.0 * n * pc.cout * (pc.cin // pc.groups) * pc.kh * pc.kw * ho * wo))
+        prof.record(e0, e1, pc, x4, ho, wo, r4 is not None, accumulate, shuffle, form)
     return out
 
 
@@ -615,6 +663,18 @@ class PackedConvTranspose:
         return ho, wo
 
 
+def mul(a, b, out=None):
+    assert a.is_contiguous() and b.is_contiguous() and a.shape == b.shape
+    if out is None:
+        out = torch.empty_like(a)
+    _check(a, b, out)
+    _call("aicg_mul", _ptr(a), _ptr(b), _ptr(out), a.numel(), _stream(a))
+    return out
+
+
+_mul = mul   # conv_transpose's `mul` parameter shadows the function
+
+
 def conv_transpose(x, pt, out=None, add=None, pre_act=ACT_NONE, pre_slope=0.0, act=ACT_NONE, act_slope=0.0, mul=None, plan_w=None):
     """y = act(conv_transpose(pre_act(x)) + bias) + add   (or ... * mul: the MDX U-Net's multiplicative skip).
     `plan_w`: as in conv() -- the row length x was cut from (1-D layers)."""
@@ -642,13 +702,14 @@ def conv_transpose(x, pt, out=None, add=None, pre_act=ACT_NONE, pre_slope=0.0, a
               pt.stride[0], pt.stride[1], pt.padding[0], pt.padding[1], act, act_slope,
               o4.stride(0), o4.stride(1), o4.stride(2), asn, asc, ash, _stream(x))
     if mul is not None:
-        globals()["mul"](out, mul, out=out)
+        _mul(out, mul, out=out)
     return out
 
 
 # ---------------------------------------------------------------------------------------------------
 # Synthesizer helpers
 # ---------------------------------------------------------------------------------------------------
+@_staged("sine_source", lambda a, k, r: (0.0, 4.0 * _numel(a[0], a[1], r)))
 def sine_source(f0, noise, upp, sr, lin_w, lin_b, sine_amp=0.1, noise_std=0.003):
     """f0: (T,) Hz; noise: (T*upp,) N(0,1) draws -> harmonic source (T*upp,) after l_linear + tanh."""
     f0 = f0.contiguous().float()
@@ -663,6 +724,7 @@ def sine_source(f0, noise, upp, sr, lin_w, lin_b, sine_amp=0.1, noise_std=0.003)
     return out
 
 
+@_staged("sine_source", lambda a, k, r: (0.0, 4.0 * _numel(a[0], r, r)))
 def sine_source_window(f0, noise, upp, sr, lin_w, lin_b, first, count, sine_amp=0.1, noise_std=0.003):
     """Samples first .. first + count - 1 of sine_source(f0, noise, ...) -- the same bits: the phase is integrated from frame 0 and sample
     n reads noise[n] of the full-length draw --, zero where that index lies outside the signal (first may be negative: the zero
@@ -721,6 +783,7 @@ def feats_prepare(feats, t_out, feats0=None, pitchf=None, protect=0.5):
     return out
 
 
+@_staged("layernorm", lambda a, k, r: (0.0, 4.0 * _numel(a[0], k.get("res"), r)))
 def layernorm_ct(x, gamma, beta, res=None, out=None, eps=1e-5):
     """LayerNorm over channels of contiguous (N, C, T); out = LN(x + res)."""
     assert x.is_contiguous() and x.dim() == 3
@@ -735,6 +798,7 @@ def layernorm_ct(x, gamma, beta, res=None, out=None, eps=1e-5):
     return out
 
 
+@_staged("groupnorm_gelu", lambda a, k, r: (0.0, 4.0 * _numel(a[0], r)))
 def rownorm_act(x, gamma, beta, act=ACT_NONE, eps=1e-5, out=None):
     """x: (rows, T), unit stride along T: per-row (x - mean)/sqrt(var + eps) * gamma + beta, then act.  x (and out) may be views of rows
     padded to a common stride (x.stride(0) >= T); `out` defaults to a buffer laid out like x.  The padding is neither read nor written.
@@ -756,6 +820,7 @@ def rownorm_act(x, gamma, beta, act=ACT_NONE, eps=1e-5, out=None):
     return out
 
 
+@_staged("attention", lambda a, k, r: (4.0 * a[0].numel() * a[0].shape[1], 4.0 * _numel(a[0], a[1], a[2], r)))      # 4 T^2 D per head
 def attention(q, k, v, n_heads, relk=None, relv_emb=None, window=0, scale=1.0, n_splits=None):
     """q, k, v: (C, T) channel-major (rows may be slices of a fused QKV buffer; stride(1) == 1).
     relk: (H, 2w+1, T) precomputed q.E^k (or None); relv_emb: (2w+1, D) for the relative value term."""
@@ -965,6 +1030,10 @@ def f0_coarse(f0, factor, mel_min, mel_max):
 # ---------------------------------------------------------------------------------------------------
 # MDX-Net helpers
 # ---------------------------------------------------------------------------------------------------
+_gemm_work = lambda a, k, r: (2.0 * r.numel() * a[1].shape[1], 4.0 * _numel(a[0], a[1], r, k.get("res")))
+
+
+@_staged("tdf_gemm_nt", _gemm_work)
 def linear_last(x, weight, bias=None, ch_scale=None, ch_shift=None, act=ACT_NONE, res=None, out=None, fp32=False):
     """nn.Linear over the last axis of a contiguous (B, C, T, F) map (+ per-channel affine, act, residual).  `fp32`: never the
     split-precision kernel (layers that select indices: CREPE)."""
@@ -980,6 +1049,15 @@ def linear_last(x, weight, bias=None, ch_scale=None, ch_shift=None, act=ACT_NONE
     _call("aicg_gemm_nt_split" if split_precision and not fp32 else "aicg_gemm_nt", _ptr(x), _ptr(weight), _ptr(bias), _ptr(ch_scale),
           _ptr(ch_shift), _ptr(res), _ptr(out), b * c * t, f, o, f, f, o, o, t, c, act, _stream(x))
     return out
+
+
+_linear_last = linear_last.__wrapped__   # the undecorated function, for dense_nt: a stage of its own, never also a tdf_gemm_nt
+
+
+@_staged("dense_gemm_nt", _gemm_work)
+def dense_nt(x, weight, bias=None, act=ACT_NONE):
+    """act(x @ weight.T + bias) for a contiguous (rows, K) matrix on the fp32 NT GEMM (CREPE's Toeplitz layers and classifier)."""
+    return _linear_last(x.view(1, 1, x.shape[0], x.shape[1]), weight, bias, act=act, fp32=True).view(x.shape[0], weight.shape[0])
 
 
 def pack_tdf_w1(w1):
@@ -1006,6 +1084,8 @@ def tdf_pair_supported(f, h, rows_per_ch):
     return bool(_lib.get().aicg_tdf_pair_supported(int(f), int(h), int(rows_per_ch)))
 
 
+# 2 GEMMs of R x F x H; x once (re-read for the residual from L2), out, weights
+@_staged("tdf_pair", lambda a, k, r: (4.0 * a[0].numel() * (a[1].numel() // a[0].shape[3]), 4.0 * _numel(a[0], r, a[1], a[1])))
 def tdf_pair(x, w1p, b1, s1, t1, w2p, b2, s2, t2, out=None):
     """x + relu(bn2(relu(bn1(x W1^T + b1)) W2^T + b2)) over the last axis of a contiguous (B, C, T, F) map, one launch.
     w1p = pack_tdf_w1(W1), w2p = pack_tdf_w2(W2)."""
@@ -1018,15 +1098,6 @@ def tdf_pair(x, w1p, b1, s1, t1, w2p, b2, s2, t2, out=None):
     _check(x, w1p, b1, s1, t1, w2p, b2, s2, t2, out)
     _call("aicg_tdf_pair", _ptr(x), _ptr(w1p), _ptr(b1), _ptr(s1), _ptr(t1), _ptr(w2p), _ptr(b2), _ptr(s2), _ptr(t2), _ptr(out),
           b * c * t, f, h, t, c, _stream(x))
-    return out
-
-
-def mul(a, b, out=None):
-    assert a.is_contiguous() and b.is_contiguous() and a.shape == b.shape
-    if out is None:
-        out = torch.empty_like(a)
-    _check(a, b, out)
-    _call("aicg_mul", _ptr(a), _ptr(b), _ptr(out), a.numel(), _stream(a))
     return out
 
 
@@ -1574,74 +1645,3 @@ def index_mix_(feats, big, best_d, best_i, rate, recompute=False):
     _call("aicg_index_mix", _ptr(feats), _ptr(big), _ptr(best_d), _ptr(best_i), feats.shape[0], feats.shape[1], float(rate),
           1 if recompute else 0, _stream(feats))
     return feats
-
-
-# ---------------------------------------------------------------------------------------------------
-# Optional per-stage accounting for bench.py's `stages` list (HIP events on the launch stream around the wrapped ops)
-# ---------------------------------------------------------------------------------------------------
-class StageProfile:
-    """name -> launches, algorithmic flops / bytes, HIP-event time.  Enabled with `ops.stage_profile = StageProfile()`."""
-
-    def __init__(self):
-        self.rec = {}
-
-    def add(self, name, e0, e1, flops, nbytes):
-        r = self.rec.setdefault(name, {"events": [], "flops": 0.0, "bytes": 0.0, "launches": 0})
-        r["events"].append((e0, e1))
-        r["flops"] += flops
-        r["bytes"] += nbytes
-        r["launches"] += 1
-
-    def summary(self):
-        torch.cuda.synchronize()
-        out = {}
-        for name, r in self.rec.items():
-            ms = sum(a.elapsed_time(b) for a, b in r["events"])
-            out[name] = {"launches": r["launches"], "ms": ms, "flops": r["flops"], "bytes": r["bytes"]}
-        return out
-
-
-stage_profile = None
-
-
-def _staged(name, fn, work):
-    """work(args, kwargs, result) -> (algorithmic flops, algorithmic HBM bytes) of one call."""
-    def wrapped(*a, **k):
-        prof = stage_profile
-        t = a[0] if a and torch.is_tensor(a[0]) else None
-        if prof is None or t is None or not t.is_cuda:
-            return fn(*a, **k)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        r = fn(*a, **k)
-        e1.record()
-        fl, by = work(a, k, r)
-        prof.add(name, e0, e1, fl, by)
-        return r
-    wrapped.__name__, wrapped.__doc__ = fn.__name__, fn.__doc__
-    return wrapped
-
-
-def _numel(*ts):
-    return float(sum(t.numel() for t in ts if t is not None))
-
-
-stft = _staged("stft", stft, lambda a, k, r: (0.0, 4.0 * _numel(a[0], r)))
-istft = _staged("istft", istft, lambda a, k, r: (0.0, 4.0 * _numel(a[0], r)))
-def dense_nt(x, weight, bias=None, act=ACT_NONE):
-    """act(x @ weight.T + bias) for a contiguous (rows, K) matrix on the fp32 NT GEMM (CREPE's Toeplitz layers and classifier)."""
-    return _linear_last_raw(x.view(1, 1, x.shape[0], x.shape[1]), weight, bias, act=act, fp32=True).view(x.shape[0], weight.shape[0])
-
-
-_linear_last_raw = linear_last
-_gemm_work = lambda a, k, r: (2.0 * r.numel() * a[1].shape[1], 4.0 * _numel(a[0], a[1], r, k.get("res")))
-linear_last = _staged("tdf_gemm_nt", linear_last, _gemm_work)
-tdf_pair = _staged("tdf_pair", tdf_pair, lambda a, k, r: (4.0 * a[0].numel() * (a[1].numel() // a[0].shape[3]),   # 2 GEMMs of R x F x H
-                                                          4.0 * _numel(a[0], r, a[1], a[1])))    # x once (re-read for the residual from L2), out, weights
-dense_nt = _staged("dense_gemm_nt", dense_nt, _gemm_work)
-attention = _staged("attention", attention, lambda a, k, r: (4.0 * a[0].numel() * a[0].shape[1],      # 4 T^2 D per head
-                                                             4.0 * _numel(a[0], a[1], a[2], r)))
-sine_source = _staged("sine_source", sine_source, lambda a, k, r: (0.0, 4.0 * _numel(a[0], a[1], r)))
-sine_source_window = _staged("sine_source", sine_source_window, lambda a, k, r: (0.0, 4.0 * _numel(a[0], r, r)))
-layernorm_ct = _staged("layernorm", layernorm_ct, lambda a, k, r: (0.0, 4.0 * _numel(a[0], k.get("res"), r)))
-rownorm_act = _staged("groupnorm_gelu", rownorm_act, lambda a, k, r: (0.0, 4.0 * _numel(a[0], r)))

@@ -1452,6 +1452,126 @@ def pitch_ac(x, sr=16000, time_step=0.01, pitch_floor=50.0, pitch_ceiling=1100.0
 
 
 # ---------------------------------------------------------------------------------------------------
+# f0_method "dio" (csrc/world_dio.hip): WORLD's DIO, StoneMask, the 3-point median
+# ---------------------------------------------------------------------------------------------------
+WORLD_DIO_NUTTALL = (0.355768, -0.487396, 0.144232, -0.012604)
+
+
+def world_dio_geometry(sr, n, frame_period=10.0, f0_floor=50.0, f0_ceil=1100.0, channels_in_octave=2.0):
+    """dict: n_frames, n_bands, n_tiles, lowcut (taps), pad, vrm, count_scratch / repair_scratch (bytes), index_ints, tile, half (per
+    band), boundary (per band, float64).  ValueError for a shape the kernels cannot serve."""
+    g = (ctypes.c_int64 * 26)()
+    b = (ctypes.c_double * 16)()
+    try:
+        _lib.call("aicg_world_dio_geometry", int(sr), int(n), float(frame_period), float(f0_floor), float(f0_ceil), float(channels_in_octave),
+                  ctypes.addressof(g), ctypes.addressof(b))
+    except RuntimeError as e:
+        raise ValueError(str(e))
+    nb = int(g[1])
+    names = ("n_frames", "n_bands", "n_tiles", "lowcut", "pad", "vrm", "count_scratch", "repair_scratch", "index_ints", "tile")
+    out = {k: int(g[i]) for i, k in enumerate(names)}
+    out["half"] = [int(g[10 + i]) for i in range(nb)]
+    out["boundary"] = np.array([b[i] for i in range(nb)], dtype=np.float64)
+    return out
+
+
+def world_dio_tables(lowcut, half):
+    """float64 taps, the low-cut's then every band's: 1 at the centre minus the Hanning low-pass 0.5 - 0.5 cos(2 pi i / (N + 1)), i = 1 ..
+    N, normalised to sum 1; per band the Nuttall window of 4 h points sampled at i / (4 h - 1)."""
+    h = 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(1, lowcut + 1, dtype=np.float64) / (lowcut + 1))
+    h = -h / h.sum()
+    h[(lowcut - 1) // 2] += 1.0
+    taps = [h]
+    for hb in half:
+        t = np.arange(4 * hb, dtype=np.float64) / (4 * hb - 1.0)
+        taps.append(sum(c * np.cos(2.0 * np.pi * k * t) for k, c in enumerate(WORLD_DIO_NUTTALL)))
+    return np.concatenate(taps)
+
+
+_world_dio_plans = {}
+
+
+def _world_dio_plan(g, device):
+    key = (g["lowcut"], tuple(g["half"]), str(device))
+    if key not in _world_dio_plans:
+        _world_dio_plans[key] = torch.from_numpy(world_dio_tables(g["lowcut"], g["half"])).to(device)
+    return _world_dio_plans[key]
+
+
+def world_dio_repair(cand, score, frame_period=10.0, f0_floor=50.0, allowed_range=0.1):
+    """Best band per frame and WORLD's four repair steps on (n_bands, n_frames) fp32 tables -> f0 float64 (n_frames,)."""
+    assert cand.dim() == 2 and cand.shape == score.shape and cand.dtype == score.dtype == torch.float32
+    assert cand.is_contiguous() and score.is_contiguous()
+    nb, nf = cand.shape
+    f0 = torch.empty((nf,), dtype=torch.float64, device=cand.device)
+    scratch = torch.empty(nf * 16 + 64, dtype=torch.uint8, device=cand.device)
+    _check(cand, score)
+    _call("aicg_world_dio_repair", _ptr(cand), _ptr(score), nb, nf, float(frame_period), float(f0_floor), float(allowed_range), _ptr(scratch),
+          _ptr(f0), _stream(cand))
+    return f0
+
+
+def world_dio(x, sr=16000, frame_period=10.0, f0_floor=50.0, f0_ceil=1100.0, channels_in_octave=2.0, allowed_range=0.1,
+              return_candidates=False, return_bands=False):
+    """pyworld.dio(x, fs, f0_floor, f0_ceil, channels_in_octave, frame_period, speed=1, allowed_range)[0] on the device.  x: 1-D float32
+    or float64 (cast on the device) -> f0 in Hz float64 (n_frames,), 0 = unvoiced [, cand, score (n_bands, n_frames) fp32, crossing
+    counts (n_bands, 4) int64 (host), the crossings themselves (integer parts int32, fractions fp32, row starts per band and kind)]
+    [, the band signals (n_bands, n) fp32: a development return].  The crossing workspace is sized from the counts, which come to the
+    host between the two calls (one small copy)."""
+    assert x.dim() == 1
+    x = x.contiguous().float()
+    n = x.numel()
+    g = world_dio_geometry(sr, n, frame_period, f0_floor, f0_ceil, channels_in_octave)
+    nb, nf, rows = g["n_bands"], g["n_frames"], 4 * g["n_bands"]
+    taps = _world_dio_plan(g, x.device)
+    scratch = torch.empty(g["count_scratch"], dtype=torch.uint8, device=x.device)
+    index = torch.empty(g["index_ints"], dtype=torch.int32, device=x.device)
+    bands = torch.zeros((nb, n), dtype=torch.float32, device=x.device) if return_bands else None
+    _check(x, taps)
+    args = (int(sr), float(frame_period), float(f0_floor), float(f0_ceil), float(channels_in_octave))
+    _call("aicg_world_dio_count", _ptr(x), n, *args, _ptr(taps), _ptr(scratch), _ptr(index), _ptr(bands) if return_bands else None, _stream(x))
+    row_start = index[2 * rows * g["n_tiles"]:].cpu().numpy().astype(np.int64)
+    total = int(row_start[-1])
+    ev_ip = torch.empty(max(total, 1), dtype=torch.int32, device=x.device)
+    ev_fr = torch.empty(max(total, 1), dtype=torch.float32, device=x.device)
+    cand = torch.empty((nb, nf), dtype=torch.float32, device=x.device)
+    score = torch.empty((nb, nf), dtype=torch.float32, device=x.device)
+    f0 = torch.empty((nf,), dtype=torch.float64, device=x.device)
+    rs = torch.empty(g["repair_scratch"], dtype=torch.uint8, device=x.device)
+    _call("aicg_world_dio", n, *args, float(allowed_range), _ptr(taps), _ptr(scratch), _ptr(index), total, _ptr(ev_ip), _ptr(ev_fr), _ptr(rs),
+          _ptr(cand), _ptr(score), _ptr(f0), _stream(x))
+    out = (f0,)
+    if return_candidates:
+        out += (cand, score, np.diff(row_start).reshape(nb, 4), (ev_ip[:total], ev_fr[:total], row_start))
+    if return_bands:
+        out += (bands,)
+    return out if len(out) > 1 else f0
+
+
+def stonemask(x, f0, sr=16000, frame_period=10.0):
+    """pyworld.stonemask(x, f0, t, fs) with t[i] = i frame_period / 1000 on the device.  x 1-D float32 / float64, f0 float64 (n_frames,) ->
+    refined f0 float64."""
+    assert x.dim() == 1 and f0.dim() == 1 and x.numel() >= 1
+    x = x.contiguous().float()
+    f0 = f0.contiguous().double()
+    out = torch.empty_like(f0)
+    _check(x, f0)
+    _call("aicg_stonemask", _ptr(x), x.numel(), int(sr), float(frame_period), _ptr(f0), f0.numel(), _ptr(out), _stream(x))
+    return out
+
+
+def medfilt3(f0):
+    """scipy.signal.medfilt(f0, 3) on a float64 track: zeros beyond both ends."""
+    assert f0.dim() == 1 and f0.dtype == torch.float64
+    f0 = f0.contiguous()
+    out = torch.empty_like(f0)
+    if f0.numel():
+        _check(f0)
+        _call("aicg_medfilt3", _ptr(f0), f0.numel(), _ptr(out), _stream(f0))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------
 # CREPE helpers
 # ---------------------------------------------------------------------------------------------------
 def frame_normalize(frames):

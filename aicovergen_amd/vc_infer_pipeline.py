@@ -256,6 +256,16 @@ class VC(object):
             f0 = torch.nn.functional.pad(f0, (pad_size, p_len - len(f0) - pad_size))
         return f0.cpu().numpy()
 
+    def get_f0_dio_computation(self, x, f0_min, f0_max):
+        """f0_method 'dio' (reference :300-309): pyworld.dio at the 10 ms frame period, pyworld.stonemask, scipy's medfilt(f0, 3) ->
+        len(x) // window + 1 frames.  The track stays on the device (ops.world_dio, ops.stonemask, ops.medfilt3); no weights, no
+        communication: every rank computes the whole contour."""
+        xd = (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))).to(self.device)
+        frame_period = self.window / self.sr * 1000
+        f0 = ops.world_dio(xd, self.sr, frame_period, float(f0_min), float(f0_max))
+        f0 = ops.medfilt3(ops.stonemask(xd, f0, self.sr, frame_period))
+        return f0.cpu().numpy()
+
     def _f0_group(self, explicit=True):
         """The process group the f0 estimators may communicate over.  Inside pipeline() the ranks of the job cut RMVPE's U-Net
         over time (rmvpe.E2E.features_sharded) and CREPE's frames (crepe.predict); a stand-alone get_f0 /
@@ -318,13 +328,15 @@ class VC(object):
             f0 = self.get_f0_official_crepe_computation(host(x), f0_min, f0_max, "tiny" if f0_method.endswith("tiny") else "full")
         elif f0_method == "pm":
             f0 = self.get_f0_pm_computation(x, f0_min, f0_max, p_len)
+        elif f0_method == "dio":
+            f0 = self.get_f0_dio_computation(x, f0_min, f0_max)
         elif "hybrid" in f0_method:
             f0 = self.get_f0_hybrid_computation(f0_method, input_audio_path, host(x), f0_min, f0_max, p_len, filter_radius,
                                                 crepe_hop_length, self.window / self.sr * 1000)
         else:
             raise NotImplementedError(
-                "f0_method %r needs pyworld, which is outside the MI355X hot path "
-                "(supported: rmvpe, pm, mangio-crepe[-tiny], crepe[-tiny], hybrid[...] of the crepe methods)" % f0_method)
+                "f0_method %r needs pyworld's harvest, which is not built for the MI355X yet "
+                "(supported: rmvpe, pm, dio, mangio-crepe[-tiny], crepe[-tiny], hybrid[...] of the crepe methods)" % f0_method)
         return np.asarray(self._estimated_f0(0, len(f0), np.asarray(f0, dtype=np.float64)), dtype=np.float64)
 
     def get_f0(self, input_audio_path, x, p_len, f0_up_key, f0_method, filter_radius, crepe_hop_length, inp_f0=None,

@@ -538,6 +538,47 @@ int aicg_pitch_ac_path(const float* cand, const int* count, int64_t n_frames, in
                        double pitch_ceiling, double octave_cost, double octave_jump_cost, double voiced_unvoiced_cost, void* scratch,
                        double* f0_out, int* state_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * f0_method "dio" (src/vc_infer_pipeline.py:300-309: pyworld.dio, pyworld.stonemask, scipy.signal.medfilt): WORLD's DIO, Morise et al.
+ * (2009, 2016), restated (csrc/world_dio.hip, tests/world_dio_ref.py).  All host arithmetic float64.
+ *
+ * aicg_world_dio_geometry: geom[0..26) = n_frames = int(1000 n / sample_rate / frame_period) + 1, n_bands = 1 + int(log2(f0_ceil /
+ *   f0_floor) channels_in_octave), tiles of the band bank, low-cut taps 2 round(sample_rate / 50) + 1, margin of the low-cut signal
+ *   (2 half[0]), voice_range_minimum, byte size of the count call's scratch and of the repair scratch, number of int32 in `index`,
+ *   the tile length, then half[b] = round(sample_rate / boundary[b] / 2) for 16 bands (0 beyond n_bands); boundary[0..16) =
+ *   f0_floor 2^((b + 1) / channels_in_octave).  AICG_E_SHAPE for more than 16 bands, a filter above 2048 taps or n >= 2^26.
+ * aicg_world_dio_count: x fp32 (n).  Mean (float64 partial sums in a fixed order), the low-cut as one FIR pass kept with its tails,
+ *   per band the Nuttall low-pass of 4 half[b] taps (delay 2 half[b] taken out), float64 accumulation; the negative-going zero
+ *   crossings of the band signal, of its negative, of its forward difference and of that one's negative are COUNTED per tile and
+ *   scanned: index = counts (4 n_bands, tiles), offsets (4 n_bands, tiles), row_start (4 n_bands + 1; the last entry is the number
+ *   of events).  taps float64: the low-cut's, then every band's.  band_out (n_bands, n) fp32 receives the band signals (development
+ *   return; may be NULL).  scratch keeps the low-cut signal for aicg_world_dio.
+ * aicg_world_dio: with ev_ip / ev_fr of n_events entries (read from row_start by the caller), the crossings are written in ascending
+ *   order per band and kind -- one-based integer sample index and fp32 fraction -- then per band, kind and frame the interval f0 is
+ *   interpolated at the frame time (bracket by binary search, end segments continued), cand (n_bands, n_frames) fp32 = the mean of
+ *   the four, score = their deviation (divisor 3) / (cand + 1e-12); a band with <= 2 intervals of any kind, or a candidate above
+ *   boundary[b], below boundary[b] / 2 or outside [f0_floor, f0_ceil], gives cand 0, score 1e17.  Then aicg_world_dio_repair.
+ * aicg_world_dio_repair: best band per frame (lowest score, ties to the lowest band), WORLD's four repair steps in float64 on the
+ *   fp32 tables -> f0_out (n_frames) float64.  One workgroup; steps 3 and 4 on one wave.  scratch: n_frames 16 + 64 bytes.
+ * aicg_stonemask: f0 (n_frames) float64 -> f0_out: WORLD's StoneMask per frame with 40 < f0 <= sample_rate / 12 (0 otherwise): the
+ *   harmonic bins of the Blackman-windowed and derivative-windowed spectra as direct DFT sums (fp32), instantaneous frequencies,
+ *   two then min(int(sample_rate / 2 / f), 6) harmonics; the initial value stays where the result is <= 0, above sample_rate / 12 or
+ *   more than 20 % away.
+ * aicg_medfilt3: out[i] = median(f0[i - 1], f0[i], f0[i + 1]) with zeros beyond both ends (scipy.signal.medfilt(f0, 3)); not in place.
+ * ---------------------------------------------------------------------------------------------- */
+int aicg_world_dio_geometry(int sample_rate, int64_t n, double frame_period, double f0_floor, double f0_ceil, double channels_in_octave,
+                            int64_t* geom, double* boundary);
+int aicg_world_dio_count(const float* x, int64_t n, int sample_rate, double frame_period, double f0_floor, double f0_ceil,
+                         double channels_in_octave, const double* taps, void* scratch, int* index, float* band_out, void* stream);
+int aicg_world_dio(int64_t n, int sample_rate, double frame_period, double f0_floor, double f0_ceil, double channels_in_octave,
+                   double allowed_range, const double* taps, const void* scratch, const int* index, int64_t n_events, int* ev_ip,
+                   float* ev_fr, void* repair_scratch, float* cand, float* score, double* f0_out, void* stream);
+int aicg_world_dio_repair(const float* cand, const float* score, int n_bands, int64_t n_frames, double frame_period, double f0_floor,
+                          double allowed_range, void* scratch, double* f0_out, void* stream);
+int aicg_stonemask(const float* x, int64_t n, int sample_rate, double frame_period, const double* f0, int64_t n_frames, double* f0_out,
+                   void* stream);
+int aicg_medfilt3(const double* f0, int64_t n, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

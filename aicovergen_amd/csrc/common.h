@@ -52,6 +52,17 @@ __host__ __device__ inline int imin(int a, int b) { return a < b ? a : b; }
 __host__ __device__ inline int imax(int a, int b) { return a > b ? a : b; }
 __host__ __device__ inline long lmin(long a, long b) { return a < b ? a : b; }
 __host__ __device__ inline long lmax(long a, long b) { return a > b ? a : b; }
+// WORLD's matlab_round: halves away from zero
+__host__ __device__ inline long mround(double v) { return v > 0 ? (long)(v + 0.5) : (long)(v - 0.5); }
+
+// workgroups of 256 threads for a grid-stride loop over `total` elements: one element a thread, at most 16 workgroups for each of 256 CUs
+inline unsigned grid_1d(long total) { return (unsigned)lmax(1, lmin((total + 255) / 256, 256L * 16)); }
+
+// 16-byte vectors at less than their natural alignment (gfx950 global memory takes unaligned dwordx4 accesses): four floats at any
+// float's address -- row c of a (C, n) signal starts at c * n floats -- and four / eight 16-bit samples
+struct __attribute__((aligned(4))) float4_u { float x, y, z, w; };
+struct __attribute__((aligned(8))) short4_t { short x, y, z, w; };
+struct __attribute__((aligned(16))) short8_t { short4_t lo, hi; };
 
 // activations shared by conv epilogues and elementwise kernels (codes: include/aicg.h).
 // The transcendental ones are kept out of line: the conv kernels instantiate the activation ~80 times per

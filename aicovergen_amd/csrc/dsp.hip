@@ -8,7 +8,7 @@
 //     resampling at mdx.py:257, librosa.resample at vc_infer_pipeline.py:641-644)
 //   * exact k = 8 nearest neighbours + inverse-square-distance feature mix -- index.search / big_npy blend (:409-431)
 // All HBM-bound except the kNN distances, which run on the conv kernel as a 1x1 GEMM (ops.py).
-#include "common.h"
+#include "reduce.h"
 
 #include <cstdint>
 
@@ -159,10 +159,6 @@ __global__ void __launch_bounds__(256) resample_poly_kernel(const float* __restr
 //   * no division in the loops: (m_hi, phase row, table row) of a lane's output advance from tile to tile and from output to
 //     output by constant (quotient, remainder) pairs.
 // One fmaf chain per output in ascending m: a fixed order, results are run-to-run identical and do not depend on the tiling.
-struct __attribute__((aligned(4))) rs_float4_u { float x, y, z, w; };   // 16 bytes at any float's address (row c starts at c * n_in)
-struct __attribute__((aligned(8))) rs_short4 { short x, y, z, w; };
-struct __attribute__((aligned(16))) rs_short8 { short a0, b0, a1, b1, a2, b2, a3, b3; };
-
 constexpr int kRsPcm16 = 0, kRsF32 = 1;   // in_format, as aicg_stem_normalise's
 constexpr int kRsThreads = 256;
 constexpr int kRsMaxRate = 1 << 20;       // up and down (gcd-reduced sample rates) the entry point accepts
@@ -225,17 +221,17 @@ __global__ void __launch_bounds__(kRsThreads) resample_poly_mc_kernel(const void
             float4 v;
             if (m >= 0 && m + 4 <= a.n_in && (FMT == kRsF32 || a.C <= 2)) {
                 if (FMT == kRsF32) {
-                    const rs_float4_u u = *reinterpret_cast<const rs_float4_u*>((const float*)x + (long)c * a.n_in + m);
+                    const float4_u u = *reinterpret_cast<const float4_u*>((const float*)x + (long)c * a.n_in + m);
                     v = make_float4(u.x, u.y, u.z, u.w);
                 } else if (a.C == 1) {
-                    const rs_short4 u = *reinterpret_cast<const rs_short4*>((const short*)x + m);
+                    const short4_t u = *reinterpret_cast<const short4_t*>((const short*)x + m);
                     const float k = 1.0f / 32768.0f;
                     v = make_float4((float)u.x * k, (float)u.y * k, (float)u.z * k, (float)u.w * k);
                 } else {
-                    const rs_short8 u = *reinterpret_cast<const rs_short8*>((const short*)x + 2 * m);
+                    const short8_t u = *reinterpret_cast<const short8_t*>((const short*)x + 2 * m);   // frames m .. m + 3, interleaved
                     const float k = 1.0f / 32768.0f;
-                    v = c == 0 ? make_float4((float)u.a0 * k, (float)u.a1 * k, (float)u.a2 * k, (float)u.a3 * k)
-                               : make_float4((float)u.b0 * k, (float)u.b1 * k, (float)u.b2 * k, (float)u.b3 * k);
+                    v = c == 0 ? make_float4((float)u.lo.x * k, (float)u.lo.z * k, (float)u.hi.x * k, (float)u.hi.z * k)
+                               : make_float4((float)u.lo.y * k, (float)u.lo.w * k, (float)u.hi.y * k, (float)u.hi.w * k);
                 }
             } else {
                 v = make_float4(rs_load1<FMT>(x, a, c, m), rs_load1<FMT>(x, a, c, m + 1), rs_load1<FMT>(x, a, c, m + 2),
@@ -366,8 +362,7 @@ __global__ void __launch_bounds__(256) ivf_scan8_kernel(const float* __restrict_
                 const float t0 = a.x - y.x, t1 = a.y - y.y, t2 = a.z - y.z, t3 = a.w - y.w;
                 acc += (t0 * t0 + t1 * t1) + (t2 * t2 + t3 * t3);
             }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+            acc = wave_sum(acc);
             // every lane of the wave now holds the same sum and the same sorted list: uniform insertion, no divergence
             const long kv = scanned + (v - b);
             if (acc < d[7] || (acc == d[7] && kv < key[7])) {

@@ -1,7 +1,7 @@
 // HBM-bound helper kernels of the RVC synthesizer: col2im for transposed convolutions, the NSF sine
 // source, the WaveNet gate, the prior sample, nearest x2 + protect blend.  One pass over the data each,
 // unit-stride along time so every wave issues full 256-byte rows.
-#include "common.h"
+#include "reduce.h"
 
 #include <cstdint>
 
@@ -247,8 +247,6 @@ __global__ void __launch_bounds__(256) feats_prepare_kernel(const float* __restr
     }
 }
 
-static unsigned ew_grid(long total) { return (unsigned)lmax(1, lmin((total + 255) / 256, 256L * 16)); }
-
 }  // namespace aicg
 
 using namespace aicg;
@@ -274,7 +272,7 @@ extern "C" int aicg_col2im(const float* cols, const float* bias, const float* ad
         else hipLaunchKernelGGL(HIP_KERNEL_NAME(col2im1d_kernel<0>), grid, dim3(256), lds, (hipStream_t)stream, p, J);
         return check_launch("col2im1d_kernel");
     }
-    hipLaunchKernelGGL(col2im_kernel, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(col2im_kernel, dim3(grid_1d(total)), dim3(256), 0, (hipStream_t)stream, p);
     return check_launch("col2im_kernel");
 }
 
@@ -285,10 +283,10 @@ extern "C" int aicg_sine_source(const float* f0, const float* noise, double* pre
     if (T == 0) return AICG_OK;
     hipLaunchKernelGGL(sine_frame_prefix_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, f0, prefix_scratch, T, upp, sr);
     if ((upp & 3) == 0 && ((uintptr_t)noise & 15) == 0 && ((uintptr_t)out & 15) == 0)
-        hipLaunchKernelGGL(sine_source4_kernel, dim3(ew_grid((long)T * (upp >> 2))), dim3(256), 0, (hipStream_t)stream, f0,
+        hipLaunchKernelGGL(sine_source4_kernel, dim3(grid_1d((long)T * (upp >> 2))), dim3(256), 0, (hipStream_t)stream, f0,
                            (const double*)prefix_scratch, noise, out, T, upp, sr, sine_amp, noise_std, lin_w, lin_b, 0L, (long)T * upp);
     else
-        hipLaunchKernelGGL(sine_source_kernel, dim3(ew_grid((long)T * upp)), dim3(256), 0, (hipStream_t)stream, f0,
+        hipLaunchKernelGGL(sine_source_kernel, dim3(grid_1d((long)T * upp)), dim3(256), 0, (hipStream_t)stream, f0,
                            (const double*)prefix_scratch, noise, out, T, upp, sr, sine_amp, noise_std, lin_w, lin_b, 0L, (long)T * upp);
     return check_launch("sine_source_kernel");
 }
@@ -310,10 +308,10 @@ extern "C" int aicg_sine_source_window(const float* f0, const float* noise, doub
         hipLaunchKernelGGL(sine_frame_prefix_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, f0, prefix_scratch, Tscan, upp, sr);
     // the form aicg_sine_source takes for this upp and noise pointer (its out is the caller's: 16-byte aligned in both calls or neither)
     if ((upp & 3) == 0 && ((uintptr_t)noise & 15) == 0 && ((uintptr_t)out & 15) == 0)
-        hipLaunchKernelGGL(sine_source4_kernel, dim3(ew_grid((long)count >> 2)), dim3(256), 0, (hipStream_t)stream, f0,
+        hipLaunchKernelGGL(sine_source4_kernel, dim3(grid_1d((long)count >> 2)), dim3(256), 0, (hipStream_t)stream, f0,
                            (const double*)prefix_scratch, noise, out, T, upp, sr, sine_amp, noise_std, lin_w, lin_b, (long)first, (long)count);
     else
-        hipLaunchKernelGGL(sine_source_kernel, dim3(ew_grid((long)count)), dim3(256), 0, (hipStream_t)stream, f0,
+        hipLaunchKernelGGL(sine_source_kernel, dim3(grid_1d((long)count)), dim3(256), 0, (hipStream_t)stream, f0,
                            (const double*)prefix_scratch, noise, out, T, upp, sr, sine_amp, noise_std, lin_w, lin_b, (long)first, (long)count);
     return check_launch("sine_source_kernel");
 }
@@ -322,7 +320,7 @@ extern "C" int aicg_gate_tanh_sigmoid(const float* a, float* out, int N, int C, 
     if (!a || !out) return fail(AICG_E_ARG, "aicg_gate_tanh_sigmoid: null pointer");
     const long total = (long)N * C * T;
     if (total == 0) return AICG_OK;
-    hipLaunchKernelGGL(gate_kernel, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream, a, out, N, C, (long)T);
+    hipLaunchKernelGGL(gate_kernel, dim3(grid_1d(total)), dim3(256), 0, (hipStream_t)stream, a, out, N, C, (long)T);
     return check_launch("gate_kernel");
 }
 
@@ -330,7 +328,7 @@ extern "C" int aicg_prior_sample(const float* stats, const float* noise, float* 
                                  void* stream) {
     if (!stats || !noise || !out) return fail(AICG_E_ARG, "aicg_prior_sample: null pointer");
     if ((long)C * T == 0) return AICG_OK;
-    hipLaunchKernelGGL(prior_sample_kernel, dim3(ew_grid((long)C * T)), dim3(256), 0, (hipStream_t)stream, stats, noise,
+    hipLaunchKernelGGL(prior_sample_kernel, dim3(grid_1d((long)C * T)), dim3(256), 0, (hipStream_t)stream, stats, noise,
                        out, C, (long)T, scale);
     return check_launch("prior_sample_kernel");
 }
@@ -365,7 +363,7 @@ __global__ void __launch_bounds__(256) axpbypcz_kernel(const float* __restrict__
 extern "C" int aicg_mul(const float* a, const float* b, float* out, int64_t n, void* stream) {
     if (!a || !b || !out) return aicg::fail(AICG_E_ARG, "aicg_mul: null pointer");
     if (n == 0) return AICG_OK;
-    hipLaunchKernelGGL(aicg::mul_kernel, dim3(aicg::ew_grid(n)), dim3(256), 0, (hipStream_t)stream, a, b, out, (long)n);
+    hipLaunchKernelGGL(aicg::mul_kernel, dim3(aicg::grid_1d(n)), dim3(256), 0, (hipStream_t)stream, a, b, out, (long)n);
     return aicg::check_launch("mul_kernel");
 }
 
@@ -373,7 +371,7 @@ extern "C" int aicg_axpbypcz(const float* a, float alpha, const float* b, float 
                              int64_t n, void* stream) {
     if (!a || !out) return aicg::fail(AICG_E_ARG, "aicg_axpbypcz: null pointer");
     if (n == 0) return AICG_OK;
-    hipLaunchKernelGGL(aicg::axpbypcz_kernel, dim3(aicg::ew_grid(n)), dim3(256), 0, (hipStream_t)stream, a, alpha, b, beta, c,
+    hipLaunchKernelGGL(aicg::axpbypcz_kernel, dim3(aicg::grid_1d(n)), dim3(256), 0, (hipStream_t)stream, a, alpha, b, beta, c,
                        gamma, out, (long)n);
     return aicg::check_launch("axpbypcz_kernel");
 }
@@ -386,17 +384,11 @@ __global__ void __launch_bounds__(256) frame_normalize_kernel(const float* __res
     const float* xr = x + (long)blockIdx.x * L;
     float s = 0.f;
     for (int i = threadIdx.x; i < L; i += 256) s += xr[i];
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-    __syncthreads();
-    const float mean = (sh[0] + sh[1] + sh[2] + sh[3]) / (float)L;
-    __syncthreads();
+    const float mean = block_sum(s, sh) / (float)L;
+    __syncthreads();   // sh is written again below
     float v = 0.f;
     for (int i = threadIdx.x; i < L; i += 256) { const float d = xr[i] - mean; v += d * d; }
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const float sd = fmaxf(1e-10f, sqrtf((sh[0] + sh[1] + sh[2] + sh[3]) / (float)(L - 1)));
+    const float sd = fmaxf(1e-10f, sqrtf(block_sum(v, sh) / (float)(L - 1)));
     float* orow = out + (long)blockIdx.x * L;
     for (int i = threadIdx.x; i < L; i += 256) orow[i] = (xr[i] - mean) / sd;
 }
@@ -428,7 +420,7 @@ extern "C" int aicg_affine_maxpool2(const float* x, const float* scale, const fl
     if (W & 1) return aicg::fail(AICG_E_SHAPE, "aicg_affine_maxpool2: W must be even");
     const long total = (long)N * C * (W / 2);
     if (total == 0) return AICG_OK;
-    hipLaunchKernelGGL(aicg::affine_maxpool2_kernel, dim3(aicg::ew_grid(total)), dim3(256), 0, (hipStream_t)stream, x, scale, shift,
+    hipLaunchKernelGGL(aicg::affine_maxpool2_kernel, dim3(aicg::grid_1d(total)), dim3(256), 0, (hipStream_t)stream, x, scale, shift,
                        out, C, W / 2, total);
     return aicg::check_launch("affine_maxpool2_kernel");
 }

@@ -12,7 +12,7 @@
 // elements j R0 ... j R0 + R0 - 1): unpadded, a 16-lane ds_write_b64 group would hit one bank pair 16 times; padded, lane stride
 // is 2 (R0 + R0 / 16) dwords and the 16 lanes of a group cover distinct banks.  All other accesses are lane-contiguous.
 #pragma once
-#include "common.h"
+#include "cplx.h"
 
 namespace aicg {
 namespace fftc {
@@ -37,8 +37,7 @@ struct Roots {
 template <int N>
 struct RootsOf { static constexpr Roots<N> v{}; };
 
-__device__ __forceinline__ float2 fadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 fsub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
+// a (c + i s): the twiddle comes split, from the constexpr root tables
 __device__ __forceinline__ float2 fmulc(float2 a, float c, float s) { return make_float2(a.x * c - a.y * s, a.x * s + a.y * c); }
 // multiplication by -i (forward) / +i (inverse)
 template <bool INV>
@@ -55,32 +54,32 @@ template <bool INV>
 struct Dft<2, INV> {
     static __device__ __forceinline__ void run(float2 (&v)[2]) {
         const float2 a = v[0], b = v[1];
-        v[0] = fadd(a, b);
-        v[1] = fsub(a, b);
+        v[0] = cadd(a, b);
+        v[1] = csub(a, b);
     }
 };
 
 template <bool INV>
 struct Dft<3, INV> {
     static __device__ __forceinline__ void run(float2 (&v)[3]) {
-        const float2 t1 = fadd(v[1], v[2]);
+        const float2 t1 = cadd(v[1], v[2]);
         const float2 t2 = make_float2(v[0].x - 0.5f * t1.x, v[0].y - 0.5f * t1.y);
-        const float2 d = fsub(v[1], v[2]);
+        const float2 d = csub(v[1], v[2]);
         const float2 t3 = rot<INV>(make_float2(0.86602540378443864676f * d.x, 0.86602540378443864676f * d.y));
-        v[0] = fadd(v[0], t1);
-        v[1] = fadd(t2, t3);
-        v[2] = fsub(t2, t3);
+        v[0] = cadd(v[0], t1);
+        v[1] = cadd(t2, t3);
+        v[2] = csub(t2, t3);
     }
 };
 
 template <bool INV>
 struct Dft<4, INV> {
     static __device__ __forceinline__ void run(float2 (&v)[4]) {
-        const float2 a = fadd(v[0], v[2]), b = fsub(v[0], v[2]), c = fadd(v[1], v[3]), d = rot<INV>(fsub(v[1], v[3]));
-        v[0] = fadd(a, c);
-        v[1] = fadd(b, d);
-        v[2] = fsub(a, c);
-        v[3] = fsub(b, d);
+        const float2 a = cadd(v[0], v[2]), b = csub(v[0], v[2]), c = cadd(v[1], v[3]), d = rot<INV>(csub(v[1], v[3]));
+        v[0] = cadd(a, c);
+        v[1] = cadd(b, d);
+        v[2] = csub(a, c);
+        v[3] = csub(b, d);
     }
 };
 
@@ -89,16 +88,16 @@ struct Dft<5, INV> {
     static __device__ __forceinline__ void run(float2 (&v)[5]) {
         constexpr float c1 = 0.30901699437494742410f, c2 = -0.80901699437494742410f;
         constexpr float s1 = 0.95105651629515357212f, s2 = 0.58778525229247312917f;
-        const float2 a1 = fadd(v[1], v[4]), a2 = fadd(v[2], v[3]), b1 = fsub(v[1], v[4]), b2 = fsub(v[2], v[3]);
+        const float2 a1 = cadd(v[1], v[4]), a2 = cadd(v[2], v[3]), b1 = csub(v[1], v[4]), b2 = csub(v[2], v[3]);
         const float2 r1 = make_float2(v[0].x + c1 * a1.x + c2 * a2.x, v[0].y + c1 * a1.y + c2 * a2.y);
         const float2 r2 = make_float2(v[0].x + c2 * a1.x + c1 * a2.x, v[0].y + c2 * a1.y + c1 * a2.y);
         const float2 i1 = rot<INV>(make_float2(s1 * b1.x + s2 * b2.x, s1 * b1.y + s2 * b2.y));
         const float2 i2 = rot<INV>(make_float2(s2 * b1.x - s1 * b2.x, s2 * b1.y - s1 * b2.y));
-        v[0] = fadd(v[0], fadd(a1, a2));
-        v[1] = fadd(r1, i1);
-        v[4] = fsub(r1, i1);
-        v[2] = fadd(r2, i2);
-        v[3] = fsub(r2, i2);
+        v[0] = cadd(v[0], cadd(a1, a2));
+        v[1] = cadd(r1, i1);
+        v[4] = csub(r1, i1);
+        v[2] = cadd(r2, i2);
+        v[3] = csub(r2, i2);
     }
 };
 

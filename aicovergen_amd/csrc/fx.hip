@@ -287,7 +287,6 @@ __global__ void __launch_bounds__(256) fx_to_pcm16_kernel(const float* __restric
     }
 }
 
-static unsigned fx_grid(long total) { return (unsigned)lmax(1, lmin((total + 255) / 256, 256L * 16)); }
 
 static long gcd_l(long a, long b) {
     while (b) { const long t = a % b; a = b; b = t; }
@@ -336,7 +335,7 @@ extern "C" int aicg_fx_reverb(const float* x, float* y, const float* state_in, f
                                                                            n_channels, (long long)n, (long long)warm);
     const long stride = fx_reverb_stride(sample_rate);
     if (n == 0) {
-        hipLaunchKernelGGL(fx_copy_state_kernel, dim3(fx_grid(stride * n_channels)), dim3(256), 0, (hipStream_t)stream, state_in,
+        hipLaunchKernelGGL(fx_copy_state_kernel, dim3(grid_1d(stride * n_channels)), dim3(256), 0, (hipStream_t)stream, state_in,
                            state_out, stride * n_channels);
         return check_launch("fx_copy_state_kernel");
     }
@@ -357,7 +356,7 @@ extern "C" int aicg_fx_to_pcm16(const float* x, int16_t* out, int n_channels, in
     if (n > 0 && (!x || !out)) return fail(AICG_E_ARG, "aicg_fx_to_pcm16: null pointer");
     if (n_channels < 1 || n < 0) return fail(AICG_E_SHAPE, "aicg_fx_to_pcm16: %d channels, n %lld", n_channels, (long long)n);
     if (n == 0) return AICG_OK;
-    hipLaunchKernelGGL(fx_to_pcm16_kernel, dim3(fx_grid(n * n_channels)), dim3(256), 0, (hipStream_t)stream, x, (short*)out, n_channels, (long)n);
+    hipLaunchKernelGGL(fx_to_pcm16_kernel, dim3(grid_1d(n * n_channels)), dim3(256), 0, (hipStream_t)stream, x, (short*)out, n_channels, (long)n);
     return check_launch("fx_to_pcm16_kernel");
 }
 
@@ -384,7 +383,7 @@ extern "C" int aicg_pcm16_mix(const int16_t* a, int a_channels, int a_rate, int6
     };
     const Pcm16Src sa = src(a, a_channels, a_rate, a_frames, a_gain1, a_gain2);
     const Pcm16Src sb = src(b, b_channels, b_rate, b_frames, b_gain1, b_gain2);
-    hipLaunchKernelGGL(pcm16_overlay_kernel, dim3(fx_grid(out_frames)), dim3(256), 0, (hipStream_t)stream, sa, sb, (short*)out,
+    hipLaunchKernelGGL(pcm16_overlay_kernel, dim3(grid_1d(out_frames)), dim3(256), 0, (hipStream_t)stream, sa, sb, (short*)out,
                        (long)out_frames, ch);
     return check_launch("pcm16_overlay_kernel");
 }

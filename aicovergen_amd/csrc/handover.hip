@@ -7,10 +7,10 @@
 // is the IEEE-rounded one (hipcc's default for `/` on float; no reciprocal multiply).
 // Both are single passes bound by HBM: 4 frames per thread and step, 16-byte loads and stores.  Row 1 of a (2, n) signal starts at
 // n floats, which is 16-byte aligned only when n % 4 == 0; float rows are therefore accessed through a 4-byte aligned vector type
-// (gfx950 global memory takes unaligned dwordx4 accesses).
+// (common.h's float4_u).
 // Non-finite samples are not numpy's: the peak is a maximum of |x| bit patterns taken with fmaxf, which skips a NaN where np.max
 // returns it, and the PCM conversion clips a NaN to -32768.  A silent stem (peak 0) divides by zero as numpy does.
-#include "common.h"
+#include "reduce.h"
 
 #include <cstdint>
 
@@ -18,17 +18,7 @@
 
 namespace aicg {
 
-struct __attribute__((aligned(4))) float4_u { float x, y, z, w; };   // 16 bytes at any float's address
-struct __attribute__((aligned(8))) short4_t { short x, y, z, w; };
-struct __attribute__((aligned(16))) short8_t { short4_t lo, hi; };
-
 constexpr int kFmtPcm16 = 0, kFmtF32 = 1;   // aicg_stem_normalise's in_format
-
-// |x| is monotone in the bit pattern of a non-negative float: one integer atomic max per wave (post.hip's absmax)
-__device__ __forceinline__ void peak_commit(float m, unsigned* __restrict__ peak_bits) {
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-    if ((threadIdx.x & 63) == 0) atomicMax(peak_bits, (unsigned)__float_as_int(m));
-}
 
 // max |x| over `total` floats
 __global__ void __launch_bounds__(256) stem_peak_f32_kernel(const float* __restrict__ x, long total, unsigned* __restrict__ peak_bits) {
@@ -144,11 +134,9 @@ __global__ void __launch_bounds__(256) mdx_stems_pcm16_kernel(const float* __res
     }
 }
 
-static unsigned stem_grid(long groups) { return (unsigned)lmax(1, lmin((groups + 255) / 256, 256L * 16)); }
-
 template <int FMT, int C>
 static void launch_divide(const void* x, float* out, long n, const float* peak, hipStream_t s) {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(stem_divide_kernel<FMT, C>), dim3(stem_grid(n / 4)), dim3(256), 0, s, x, out, n, peak);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(stem_divide_kernel<FMT, C>), dim3(grid_1d(n / 4)), dim3(256), 0, s, x, out, n, peak);
 }
 
 }  // namespace aicg
@@ -167,9 +155,9 @@ extern "C" int aicg_stem_normalise(const void* x, int in_format, int n_channels,
     if (n == 0) return AICG_OK;
     const long total = (long)n * n_channels;
     if (in_format == kFmtF32)
-        hipLaunchKernelGGL(stem_peak_f32_kernel, dim3(stem_grid(total / 4)), dim3(256), 0, s, (const float*)x, total, (unsigned*)peak);
+        hipLaunchKernelGGL(stem_peak_f32_kernel, dim3(grid_1d(total / 4)), dim3(256), 0, s, (const float*)x, total, (unsigned*)peak);
     else
-        hipLaunchKernelGGL(stem_peak_pcm16_kernel, dim3(stem_grid(total / 8)), dim3(256), 0, s, (const short*)x, total, (unsigned*)peak);
+        hipLaunchKernelGGL(stem_peak_pcm16_kernel, dim3(grid_1d(total / 8)), dim3(256), 0, s, (const short*)x, total, (unsigned*)peak);
     const int rc = check_launch("stem_peak_kernel");
     if (rc != AICG_OK) return rc;
     if (in_format == kFmtF32) {
@@ -189,7 +177,7 @@ extern "C" int aicg_mdx_stems_pcm16(const float* wave, const float* separated, c
         return fail(AICG_E_ARG, "aicg_mdx_stems_pcm16: inputs must be 4-byte, outputs 16-byte aligned");
     if (main_out && main_out == inverted_out) return fail(AICG_E_ARG, "aicg_mdx_stems_pcm16: the two outputs are the same buffer");
     if (n == 0) return AICG_OK;
-    hipLaunchKernelGGL(mdx_stems_pcm16_kernel, dim3(stem_grid(n / 4)), dim3(256), 0, (hipStream_t)stream, wave, separated, peak,
+    hipLaunchKernelGGL(mdx_stems_pcm16_kernel, dim3(grid_1d(n / 4)), dim3(256), 0, (hipStream_t)stream, wave, separated, peak,
                        compensation, (long)n, (short*)main_out, (short*)inverted_out);
     return check_launch("mdx_stems_pcm16_kernel");
 }

@@ -4,7 +4,7 @@
 //                     attentions.Encoder.forward :61-73 as norm(x + y); HuBERT encoder LayerNorms)
 //   * rownorm_act  : per-row mean/variance over time + affine + activation: HuBERT feature-extractor
 //                    GroupNorm(512 groups == 512 channels) + GELU (fairseq ConvFeatureExtractionModel layer 0)
-#include "common.h"
+#include "reduce.h"
 
 #include <cstdint>
 
@@ -120,13 +120,13 @@ __global__ void __launch_bounds__(1024) layernorm_ct_reg_kernel(const float* __r
     }
 }
 
-__device__ __forceinline__ float block_sum_256(float v, float* sh) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    const int w = threadIdx.x >> 6;
+// reduce.h's block_sum with the barrier that lets sh be used again, between the wave step and the store
+__device__ __forceinline__ float block_sum_again(float v, float* sh) {
+    v = wave_sum(v);
     __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[w] = v;
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
     __syncthreads();
-    return sh[0] + sh[1] + sh[2] + sh[3];
+    return ((sh[0] + sh[1]) + sh[2]) + sh[3];
 }
 
 // one workgroup per row (channel): mean, variance (two passes), then normalise + act
@@ -138,13 +138,13 @@ __global__ void __launch_bounds__(256) rownorm_act_kernel(const float* __restric
     const float* xr = x + row * ld;
     float s = 0.f;
     for (long t = threadIdx.x; t < T; t += 256) s += xr[t];
-    const float mean = block_sum_256(s, sh) / (float)T;
+    const float mean = block_sum_again(s, sh) / (float)T;
     float v = 0.f;
     for (long t = threadIdx.x; t < T; t += 256) {
         const float d = xr[t] - mean;
         v += d * d;
     }
-    const float var = block_sum_256(v, sh) / (float)T;
+    const float var = block_sum_again(v, sh) / (float)T;
     const float rstd = rsqrtf(var + eps);
     const float g = gamma ? gamma[row] : 1.f, b = beta ? beta[row] : 0.f;
     float* orow = out + row * ld;

@@ -1,16 +1,18 @@
 // f0_method "pm" on the device (reference src/vc_infer_pipeline.py:279-294, parselmouth's Sound.to_pitch_ac): Praat's autocorrelation
 // pitch -- Boersma (1993), "Accurate short-term analysis of the fundamental frequency and the harmonics-to-noise ratio of a sampled
 // sound" -- in three stages:
-//   * pitch_ac_sum_kernel / pitch_ac_peak_kernel: the global mean (float64 partial sums, added in a fixed order) and the global
-//     peak max |x - mean| (post.hip's absmax pattern on the mean-removed signal);
+//   * sum_f64_partials_kernel / pitch_ac_peak_kernel: the global mean (float64 partial sums, added in a fixed order) and the global
+//     peak max |x - mean| (peak_commit on the mean-removed signal);
 //   * pitch_ac_frame_kernel: one workgroup per frame -- mean removal, Hanning window, autocorrelation through two 2048-point complex
 //     FFTs in LDS (forward decimation in frequency, |X|^2 in the scrambled order, the mirrored decimation in time back: no reordering
 //     pass), normalisation by the window's autocorrelation, maxima, sinc-interpolated strengths, the 14 strongest, golden-section
 //     refinement.  A group of 16 lanes shares one interpolation sum; its partial sums meet in a fixed butterfly;
 //   * pitch_ac_nodes_kernel / pitch_ac_path_kernel: Praat's Pitch_pathFinder in float64 -- node values and log2 f of every candidate in
 //     parallel, then one wave walks the frames (four predecessors per lane), back-pointers in scratch, backtracking through LDS.
-// Nothing here uses a floating-point atomic: two calls give the same bits.
-#include "common.h"
+// Nothing here uses a floating-point atomic, and the sums over a wave, a workgroup and the whole signal are reduce.h's, which defines
+// their order: two calls give the same bits.
+#include "cplx.h"
+#include "reduce.h"
 
 #include <cmath>
 
@@ -22,7 +24,6 @@ constexpr int kAcGroups = kAcThreads / kAcGroup;    // = the most candidates a f
 constexpr int kAcDepthStrength = 30, kAcDepthRefine = 70, kAcDepthRefineHigh = 700;
 constexpr int kAcGoldenSteps = 20;                  // bracket [k - 1, k + 1] -> 2 * 0.618^20 = 1.3e-4 samples
 constexpr float kAcGolden = 0.61803398874989484820f;
-constexpr int kAcSumBlocks = 256;                   // partial sums of the global mean
 constexpr int kAcMaxFft = 4096;
 
 struct AcGeom {
@@ -52,41 +53,20 @@ static int ac_geom(const char* who, int sr, long n, double dt, double fl, double
     if (g->n_frames < 1 || nw > n) return fail(AICG_E_SHAPE, "%s: %ld samples are shorter than one window (%ld)", who, n, nw);
     g->step = dt * (double)sr;
     g->t1s = 0.5 * (double)n - 0.5 * (double)(g->n_frames - 1) * g->step;
-    g->cand_scratch = (long)sizeof(double) * (kAcSumBlocks + 2);
+    g->cand_scratch = (long)sizeof(double) * (kSumPartials + 2);
     g->path_scratch = g->n_frames * (long)(16 * 2 * sizeof(double) + 16);
     return AICG_OK;
 }
 
 // ---- global mean and peak --------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum_f64(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// part[b] = sum of block b's contiguous share of x, float64
-__global__ void __launch_bounds__(256) pitch_ac_sum_kernel(const float* __restrict__ x, long n, double* __restrict__ part) {
-    __shared__ double ws[4];
-    const long per = ldiv_up(n, (long)gridDim.x), lo = (long)blockIdx.x * per, hi = lmin(n, lo + per);
-    double s = 0.0;
-    for (long i = lo + threadIdx.x; i < hi; i += 256) s += (double)x[i];
-    s = wave_sum_f64(s);
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = ((ws[0] + ws[1]) + ws[2]) + ws[3];
-}
-
-// every wave adds the partial sums in the same order; stats[0] = mean (fp32), stats[1] = max |x - mean| (bits of a non-negative float)
+// stats[0] = mean (fp32, the same bits in every thread), stats[1] = max |x - mean| (bits of a non-negative float)
 __global__ void __launch_bounds__(256) pitch_ac_peak_kernel(const float* __restrict__ x, long n, const double* __restrict__ part, int n_part,
                                                             float* __restrict__ stats) {
-    double s = 0.0;
-    for (int b = threadIdx.x & 63; b < n_part; b += 64) s += part[b];
-    s = wave_sum_f64(s);   // the same tree in every wave: every thread holds the same bits
-    const float mean = (float)(s / (double)n);
+    const float mean = (float)(sum_of_partials(part, n_part) / (double)n);
     if (blockIdx.x == 0 && threadIdx.x == 0) stats[0] = mean;
     float m = 0.f;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) m = fmaxf(m, fabsf(x[i] - mean));
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    if ((threadIdx.x & 63) == 0) atomicMax(reinterpret_cast<unsigned*>(stats + 1), (unsigned)__float_as_int(m));
+    peak_commit(m, reinterpret_cast<unsigned*>(stats + 1));
 }
 
 // ---- the frame stage ---------------------------------------------------------------------------------------------------------
@@ -97,11 +77,6 @@ struct AcFrameParams {
     int max_cand, list_cap;
     float sr, floor_hz, vthr, sil, octcost;
 };
-
-__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ float2 cmul(float2 a, float2 w) { return make_float2(a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x); }
-__device__ __forceinline__ float2 cmulc(float2 a, float2 w) { return make_float2(a.x * w.x + a.y * w.y, a.y * w.x - a.x * w.y); }   // a conj(w)
 
 // One radix-4 stage over blocks of L points, in place.  Forward (decimation in frequency): butterfly, then twiddles W_L^{j m}; the
 // inverse stage undoes it up to the factor 4: conjugate twiddles, then the conjugate butterfly.  tw[k] = exp(-2 pi i k / N).
@@ -460,13 +435,12 @@ extern "C" int aicg_pitch_ac_candidates(const float* x, int64_t n, int sample_ra
     if (!x || !window || !window_ac || !twiddle || !scratch || !cand || !count) return fail(AICG_E_ARG, "aicg_pitch_ac_candidates: null pointer");
     hipStream_t st = (hipStream_t)stream;
     double* part = (double*)scratch;
-    float* stats = (float*)(part + kAcSumBlocks);
+    float* stats = (float*)(part + kSumPartials);
     (void)hipMemsetAsync(stats, 0, 2 * sizeof(float), st);
-    hipLaunchKernelGGL(pitch_ac_sum_kernel, dim3(kAcSumBlocks), dim3(256), 0, st, x, (long)n, part);
-    int rc2 = check_launch("pitch_ac_sum_kernel");
+    hipLaunchKernelGGL(sum_f64_partials_kernel, dim3(kSumPartials), dim3(256), 0, st, x, (long)n, part);
+    int rc2 = check_launch("sum_f64_partials_kernel");
     if (rc2 != AICG_OK) return rc2;
-    const unsigned pg = (unsigned)lmax(1, lmin(((long)n + 255) / 256, 256L * 16));
-    hipLaunchKernelGGL(pitch_ac_peak_kernel, dim3(pg), dim3(256), 0, st, x, (long)n, (const double*)part, kAcSumBlocks, stats);
+    hipLaunchKernelGGL(pitch_ac_peak_kernel, dim3(grid_1d((long)n)), dim3(256), 0, st, x, (long)n, (const double*)part, kSumPartials, stats);
     rc2 = check_launch("pitch_ac_peak_kernel");
     if (rc2 != AICG_OK) return rc2;
     AcFrameParams p;

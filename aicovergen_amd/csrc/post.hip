@@ -3,7 +3,7 @@
 //   * change_rms: librosa.feature.rms envelopes, linear interpolation, power-law mix (:41-60)
 //   * peak limit + truncating int16 conversion (:645-649)
 // All HBM-bound single passes; float64 where the reference computes in float64 (filtered audio, box sums).
-#include "common.h"
+#include "reduce.h"
 
 namespace aicg {
 
@@ -94,9 +94,7 @@ __global__ void __launch_bounds__(256) rms_mix_kernel(float* __restrict__ data, 
 __global__ void __launch_bounds__(256) absmax_kernel(const float* __restrict__ x, long n, unsigned* __restrict__ out_bits) {
     float m = 0.f;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) m = fmaxf(m, fabsf(x[i]));
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-    // non-negative floats order like their bit patterns: one integer atomic max per wave
-    if ((threadIdx.x & 63) == 0) atomicMax(out_bits, (unsigned)__float_as_int(m));
+    peak_commit(m, out_bits);
 }
 
 // (x * scale).astype(int16): C-style truncation toward zero
@@ -105,8 +103,6 @@ __global__ void __launch_bounds__(256) to_int16_kernel(const float* __restrict__
         out[i] = (short)(int)(x[i] * scale);
 }
 
-static unsigned pgrid(long total) { return (unsigned)lmax(1, lmin((total + 255) / 256, 256L * 16)); }
-
 }  // namespace aicg
 
 using namespace aicg;
@@ -114,7 +110,7 @@ using namespace aicg;
 extern "C" int aicg_box_sum_f64(const double* x, double* out, int64_t n, int window, void* stream) {
     if (!x || !out) return fail(AICG_E_ARG, "aicg_box_sum_f64: null pointer");
     if (n <= 0) return AICG_OK;
-    hipLaunchKernelGGL(box_sum_f64_kernel, dim3(pgrid(n)), dim3(256), 0, (hipStream_t)stream, x, out, (long)n, window);
+    hipLaunchKernelGGL(box_sum_f64_kernel, dim3(grid_1d(n)), dim3(256), 0, (hipStream_t)stream, x, out, (long)n, window);
     return check_launch("box_sum_f64_kernel");
 }
 
@@ -144,7 +140,7 @@ extern "C" int aicg_rms_mix(float* data, int64_t n, const double* rms1, int64_t 
                             void* stream) {
     if (!data || !rms1 || !rms2) return fail(AICG_E_ARG, "aicg_rms_mix: null pointer");
     if (n <= 0) return AICG_OK;
-    hipLaunchKernelGGL(rms_mix_kernel, dim3(pgrid(n)), dim3(256), 0, (hipStream_t)stream, data, (long)n, rms1, (long)m1, rms2,
+    hipLaunchKernelGGL(rms_mix_kernel, dim3(grid_1d(n)), dim3(256), 0, (hipStream_t)stream, data, (long)n, rms1, (long)m1, rms2,
                        (long)m2, rate);
     return check_launch("rms_mix_kernel");
 }
@@ -153,13 +149,13 @@ extern "C" int aicg_absmax(const float* x, int64_t n, float* out, void* stream) 
     if (!x || !out) return fail(AICG_E_ARG, "aicg_absmax: null pointer");
     (void)hipMemsetAsync(out, 0, sizeof(float), (hipStream_t)stream);
     if (n <= 0) return AICG_OK;
-    hipLaunchKernelGGL(absmax_kernel, dim3(pgrid(n)), dim3(256), 0, (hipStream_t)stream, x, (long)n, (unsigned*)out);
+    hipLaunchKernelGGL(absmax_kernel, dim3(grid_1d(n)), dim3(256), 0, (hipStream_t)stream, x, (long)n, (unsigned*)out);
     return check_launch("absmax_kernel");
 }
 
 extern "C" int aicg_to_int16(const float* x, int16_t* out, int64_t n, float scale, void* stream) {
     if (!x || !out) return fail(AICG_E_ARG, "aicg_to_int16: null pointer");
     if (n <= 0) return AICG_OK;
-    hipLaunchKernelGGL(to_int16_kernel, dim3(pgrid(n)), dim3(256), 0, (hipStream_t)stream, x, (short*)out, (long)n, scale);
+    hipLaunchKernelGGL(to_int16_kernel, dim3(grid_1d(n)), dim3(256), 0, (hipStream_t)stream, x, (short*)out, (long)n, scale);
     return check_launch("to_int16_kernel");
 }

@@ -441,7 +441,6 @@ __global__ void __launch_bounds__(256) f0_coarse_kernel(const double* __restrict
     }
 }
 
-static unsigned ew_grid2(long total) { return (unsigned)lmax(1, lmin((total + 255) / 256, 256L * 16)); }
 
 }  // namespace aicg
 
@@ -450,7 +449,7 @@ using namespace aicg;
 extern "C" int aicg_complex_abs(const float* re, const float* im, float* out, int64_t n, void* stream) {
     if (!re || !im || !out) return fail(AICG_E_ARG, "aicg_complex_abs: null pointer");
     if (n == 0) return AICG_OK;
-    hipLaunchKernelGGL(cabs_kernel, dim3(ew_grid2(n)), dim3(256), 0, (hipStream_t)stream, re, im, out, (long)n);
+    hipLaunchKernelGGL(cabs_kernel, dim3(grid_1d(n)), dim3(256), 0, (hipStream_t)stream, re, im, out, (long)n);
     return check_launch("cabs_kernel");
 }
 
@@ -459,7 +458,7 @@ extern "C" int aicg_channel_affine(const float* x, const float* scale, const flo
     if (!x || !scale || !shift || !out) return fail(AICG_E_ARG, "aicg_channel_affine: null pointer");
     const long total = (long)N * C * HW;
     if (total == 0) return AICG_OK;
-    hipLaunchKernelGGL(channel_affine_kernel, dim3(ew_grid2(total)), dim3(256), 0, (hipStream_t)stream, x, scale, shift, out, C,
+    hipLaunchKernelGGL(channel_affine_kernel, dim3(grid_1d(total)), dim3(256), 0, (hipStream_t)stream, x, scale, shift, out, C,
                        (long)HW, total, act);
     return check_launch("channel_affine_kernel");
 }
@@ -470,7 +469,7 @@ extern "C" int aicg_avgpool2x2(const float* x, float* out, int N, int C, int H, 
     const int Ho = H / 2, Wo = W / 2;
     const long total = (long)N * C * Ho * Wo;
     if (total == 0) return AICG_OK;
-    hipLaunchKernelGGL(avgpool2x2_kernel, dim3(ew_grid2(total)), dim3(256), 0, (hipStream_t)stream, x, out, N, C, Ho, Wo,
+    hipLaunchKernelGGL(avgpool2x2_kernel, dim3(grid_1d(total)), dim3(256), 0, (hipStream_t)stream, x, out, N, C, Ho, Wo,
                        (long)x_sn, (long)x_sc, (long)x_sh);
     return check_launch("avgpool2x2_kernel");
 }
@@ -577,7 +576,7 @@ extern "C" int aicg_f0_coarse(const double* f0_in, double factor, double* f0_out
                               double mel_max, void* stream) {
     if (!f0_in || !f0_out || !coarse) return fail(AICG_E_ARG, "aicg_f0_coarse: null pointer");
     if (n == 0) return AICG_OK;
-    hipLaunchKernelGGL(f0_coarse_kernel, dim3(ew_grid2(n)), dim3(256), 0, (hipStream_t)stream, f0_in, factor, f0_out,
+    hipLaunchKernelGGL(f0_coarse_kernel, dim3(grid_1d(n)), dim3(256), 0, (hipStream_t)stream, f0_in, factor, f0_out,
                        (long*)coarse, (long)n, mel_min, mel_max);
     return check_launch("f0_coarse_kernel");
 }

@@ -16,13 +16,6 @@
 
 namespace aicg {
 
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) {
-    return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ float2 cconj(float2 a) { return make_float2(a.x, -a.y); }
-
 // tw[i] = exp(-2 pi i * i / M).  INV conjugates it.
 template <bool INV>
 __device__ __forceinline__ float2 twiddle(const float2* __restrict__ tw, int i) {
@@ -235,7 +228,8 @@ __global__ void __launch_bounds__(256) istft_ola_kernel(const float* __restrict_
 }
 
 // ---- compile-time-plan kernels (fft_reg.h): one workgroup = FR frames, three register passes ------------------------------------------
-__device__ __forceinline__ int reflect_index(int n, int L) {
+// index n of the signal reflected once about either end (center=True pads by n_fft / 2 < L; post.hip's reflect_index repeats the fold)
+__device__ __forceinline__ int reflect_once(int n, int L) {
     if (n < 0) n = -n;
     if (n >= L) n = 2 * (L - 1) - n;
     return n;
@@ -263,7 +257,7 @@ __global__ void __launch_bounds__(P::NT) stft_reg_kernel(StftArgs p) {
             const int m = j + u * P::T0;
             const int n0 = n_base + 2 * m;
             const float2 w = win[m];
-            const float a = xs[inside ? n0 : reflect_index(n0, p.L)], b = xs[inside ? n0 + 1 : reflect_index(n0 + 1, p.L)];
+            const float a = xs[inside ? n0 : reflect_once(n0, p.L)], b = xs[inside ? n0 + 1 : reflect_once(n0 + 1, p.L)];
             v[u] = make_float2(a * w.x, b * w.y);
         }
         Dft<R0, false>::run(v);

@@ -1,7 +1,7 @@
 // f0_method "dio" on the device (reference src/vc_infer_pipeline.py:300-309: pyworld.dio, pyworld.stonemask, scipy's medfilt): WORLD's
 // DIO -- Morise, Kawahara, Katayose (2009), "Fast and reliable F0 estimation method based on the period extraction of vocal fold
 // vibration of singing voice and speech"; Morise et al. (2016), "WORLD" -- restated (tests/world_dio_ref.py):
-//   * dio_sum_kernel: the global mean, float64 partial sums added in a fixed order;
+//   * sum_f64_partials_kernel: the global mean, float64 partial sums added in a fixed order;
 //   * dio_lowcut_kernel: the 2 round(sr / 50) + 1 tap low-cut as one FIR pass over the mean-removed signal, written with the margin of
 //     2 half[0] samples on either side that the widest band filter reads (nothing is cut between the two filters);
 //   * dio_band_kernel<EMIT>: one workgroup per (tile of 1024 samples, band): the Nuttall FIR from one LDS tile plus halo, taps in LDS,
@@ -13,8 +13,8 @@
 //   * dio_repair_kernel: one workgroup -- best band per frame, the four repair steps; steps 3 and 4 walk on one wave, bands across lanes;
 //   * stonemask_kernel: one workgroup per frame, the <= 6 harmonic bins of the two windowed spectra as direct DFT sums;
 //   * medfilt3_kernel.
-// No atomics: two calls give the same bits.
-#include "common.h"
+// No atomics, and the sums over a wave and over the whole signal are reduce.h's, which defines their order: two calls give the same bits.
+#include "reduce.h"
 
 #include <cmath>
 
@@ -24,13 +24,10 @@ constexpr int kDioThreads = 256;
 constexpr int kDioTile = 1024;                      // samples a workgroup of the band bank owns (4 a thread)
 constexpr int kDioMaxBands = 16;
 constexpr int kDioMaxTaps = 2048;                   // the longest filter the LDS tile is laid out for
-constexpr int kDioSumBlocks = 256;
 constexpr int kStoneMaxWindow = 4096;
 constexpr double kDioEps = 1e-12;                   // the safeguard in denominators
 constexpr float kDioRejected = 1.0e17f;             // 100000 / (0 + 1e-12): the score of a rejected candidate
 constexpr double kStoneFloor = 40.0;
-
-static inline long dio_mround(double v) { return v > 0 ? (long)(v + 0.5) : (long)(v - 0.5); }
 
 struct DioGeom {
     long n, n_frames, n_tiles;
@@ -52,38 +49,22 @@ static int dio_geom(const char* who, int sr, long n, double fp, double fl, doubl
     g->n_bands = (int)nb;
     for (int b = 0; b < g->n_bands; ++b) {
         g->boundary[b] = fl * pow(2.0, ((double)b + 1.0) / cio);
-        g->half[b] = (int)dio_mround((double)sr / g->boundary[b] / 2.0);
+        g->half[b] = (int)mround((double)sr / g->boundary[b] / 2.0);
         if (g->half[b] < 1 || 4 * g->half[b] > kDioMaxTaps)
             return fail(AICG_E_SHAPE, "%s: band %d needs %d taps (4 .. %d)", who, b, 4 * g->half[b], kDioMaxTaps);
     }
-    g->lowcut = 2 * (int)dio_mround((double)sr / 50.0) + 1;
+    g->lowcut = 2 * (int)mround((double)sr / 50.0) + 1;
     if (g->lowcut > kDioMaxTaps) return fail(AICG_E_SHAPE, "%s: a low-cut of %d taps at %d Hz (at most %d)", who, g->lowcut, sr, kDioMaxTaps);
     g->pad = 2 * g->half[0];
     g->vrm = 2 * (int)(0.5 + 1000.0 / fp / fl) + 1;
     g->n_tiles = lmax(1, ldiv_up(n, (long)kDioTile));
-    g->count_scratch = (long)sizeof(double) * kDioSumBlocks + (long)sizeof(float) * (n + 2 * g->pad);
+    g->count_scratch = (long)sizeof(double) * kSumPartials + (long)sizeof(float) * (n + 2 * g->pad);
     g->repair_scratch = g->n_frames * 16 + 64;
     g->index_ints = 2 * 4 * g->n_bands * g->n_tiles + 4 * g->n_bands + 1;
     return AICG_OK;
 }
 
-// ---- mean -----------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double dio_wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__global__ void __launch_bounds__(256) dio_sum_kernel(const float* __restrict__ x, long n, double* __restrict__ part) {
-    __shared__ double ws[4];
-    const long per = ldiv_up(n, (long)gridDim.x), lo = (long)blockIdx.x * per, hi = lmin(n, lo + per);
-    double s = 0.0;
-    for (long i = lo + threadIdx.x; i < hi; i += 256) s += (double)x[i];
-    s = dio_wave_sum(s);
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = ((ws[0] + ws[1]) + ws[2]) + ws[3];
-}
-
+// ---- low-cut --------------------------------------------------------------------------------------------------------------------
 // out[j] = sum_k tr[k] xs[j + k], float64, for the j this thread owns (j = tid, tid + 256, ...)
 __device__ __forceinline__ double dio_fir_at(const double* tr, const double* xs, int K, int j) {
     double a0 = 0.0, a1 = 0.0;
@@ -103,9 +84,7 @@ __global__ void __launch_bounds__(kDioThreads) dio_lowcut_kernel(const float* __
     double* tr = smem;              // [N] reversed taps
     double* xs = smem + N;          // [kDioTile + N - 1]
     const int tid = threadIdx.x, c = (N - 1) / 2;
-    double s = 0.0;
-    for (int b = tid & 63; b < kDioSumBlocks; b += 64) s += part[b];
-    const double mean = dio_wave_sum(s) / (double)n;    // the same tree in every wave
+    const double mean = sum_of_partials(part, kSumPartials) / (double)n;
     const long q0 = (long)blockIdx.x * kDioTile, total = n + 2 * (long)pad;
     for (int k = tid; k < N; k += kDioThreads) tr[k] = taps[N - 1 - k];
     for (int m = tid; m < kDioTile + N - 1; m += kDioThreads) {
@@ -392,8 +371,6 @@ struct StoneParams {
     double fs, frame_period;
 };
 
-__device__ __forceinline__ long stone_mround(double v) { return v > 0 ? (long)(v + 0.5) : (long)(v - 0.5); }
-
 // the amplitude-weighted instantaneous frequency over nh harmonics of f (P, Q: power and cross term of the bins, in the order asked)
 __device__ __forceinline__ double stone_fix(const float* P, const float* Q, const int* bin, int nh, int fft_size, double fs) {
 #pragma clang fp contract(off)
@@ -426,7 +403,7 @@ __global__ void __launch_bounds__(kDioThreads) stonemask_kernel(const float* __r
         const double t = (double)fi * p.frame_period / 1000.0;
         const int half = (int)(1.5 * p.fs / f0 + 1.0), W = 2 * half + 1;
         const int fft_size = 1 << (2 + (31 - __builtin_clz((unsigned)W)));
-        const long idx0 = stone_mround((t - (double)half / p.fs) * p.fs + 0.001);
+        const long idx0 = mround((t - (double)half / p.fs) * p.fs + 0.001);
         for (int j = tid; j < W; j += kDioThreads) {
             const double tm = (((double)(idx0 + j) - 1.0) / p.fs - t) / ((double)W / p.fs);
             wn[j] = (float)(0.42 + 0.5 * cos(2.0 * 3.14159265358979323846 * tm) + 0.08 * cos(4.0 * 3.14159265358979323846 * tm));
@@ -443,7 +420,7 @@ __global__ void __launch_bounds__(kDioThreads) stonemask_kernel(const float* __r
         for (int pass = 0; pass < 2; ++pass) {
             const int nh = pass == 0 ? 2 : imin((int)(p.fs / 2.0 / f), 6);
             for (int k = 1; k <= nh; ++k) {
-                const int b = (int)stone_mround(f * (double)fft_size / p.fs * (double)k);
+                const int b = (int)mround(f * (double)fft_size / p.fs * (double)k);
                 float re = 0.f, im = 0.f, dre = 0.f, dim = 0.f;
                 for (int j = tid; j < W; j += kDioThreads) {
                     const int r = (int)(((long)b * j) & (fft_size - 1));
@@ -452,7 +429,7 @@ __global__ void __launch_bounds__(kDioThreads) stonemask_kernel(const float* __r
                     re += wa[j] * cs; im -= wa[j] * sn;
                     dre += wd[j] * cs; dim -= wd[j] * sn;
                 }
-                for (int o = 32; o > 0; o >>= 1) {
+                for (int o = 32; o > 0; o >>= 1) {   // four of reduce.h's wave_sum, interleaved
                     re += __shfl_xor(re, o, 64); im += __shfl_xor(im, o, 64);
                     dre += __shfl_xor(dre, o, 64); dim += __shfl_xor(dim, o, 64);
                 }
@@ -548,9 +525,9 @@ extern "C" int aicg_world_dio_count(const float* x, int64_t n, int sample_rate, 
         return AICG_OK;
     }
     double* part = (double*)scratch;
-    float* lc = (float*)(part + kDioSumBlocks);
-    hipLaunchKernelGGL(dio_sum_kernel, dim3(kDioSumBlocks), dim3(256), 0, st, x, (long)n, part);
-    int rc2 = check_launch("dio_sum_kernel");
+    float* lc = (float*)(part + kSumPartials);
+    hipLaunchKernelGGL(sum_f64_partials_kernel, dim3(kSumPartials), dim3(256), 0, st, x, (long)n, part);
+    int rc2 = check_launch("sum_f64_partials_kernel");
     if (rc2 != AICG_OK) return rc2;
     const size_t lds_lc = sizeof(double) * (size_t)(2 * g.lowcut + kDioTile - 1);
     allow_dynamic_lds((const void*)dio_lowcut_kernel, lds_lc);
@@ -585,7 +562,7 @@ extern "C" int aicg_world_dio(int64_t n, int sample_rate, double frame_period, d
     const int* offs = index + (long)rows * g.n_tiles;
     const int* row_start = offs + (long)rows * g.n_tiles;
     if (n > 0 && n_events > 0) {
-        const float* lc = (const float*)((const double*)scratch + kDioSumBlocks);
+        const float* lc = (const float*)((const double*)scratch + kSumPartials);
         DioBands bp;
         dio_bands(g, &bp);
         const size_t lds = dio_band_lds(g.half[0]);

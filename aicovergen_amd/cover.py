@@ -824,7 +824,7 @@ def build_parser():
     p.add_argument("-ir", "--index-rate", type=float, default=0.5, help="How much of the retrieved features to mix in (0 to 1)")
     p.add_argument("-fr", "--filter-radius", type=int, default=3, help="Median filtering radius of the harvested pitch (0 to 7)")
     p.add_argument("-rms", "--rms-mix-rate", type=float, default=0.25, help="How much to use the original vocal's loudness (0) or a fixed loudness (1)")
-    p.add_argument("-palgo", "--pitch-detection-algo", type=str, default="rmvpe", help="rmvpe, mangio-crepe, pm or dio (pm and dio need no rmvpe.pt)")
+    p.add_argument("-palgo", "--pitch-detection-algo", type=str, default="rmvpe", help="rmvpe, mangio-crepe, pm, dio or hybrid[dio+mangio-crepe+...] (pm and dio need no rmvpe.pt)")
     p.add_argument("-hop", "--crepe-hop-length", type=int, default=128, help="Hop length of mangio-crepe")
     p.add_argument("-pro", "--protect", type=float, default=0.33, help="Protection of voiceless consonants and breath sounds (0.5 disables it)")
     p.add_argument("-mv", "--main-vol", type=int, default=0, help="Volume change for AI main vocals in decibels")

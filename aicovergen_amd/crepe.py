@@ -166,10 +166,27 @@ def predict(net, audio, hop, fmin=50.0, fmax=1100.0, batch_size=None, dither=Non
     return (10 * 2 ** (cents / 1200)), bins, post
 
 
+DEVICE_QUANTILE = True   # a tensor's 0.999 quantile and the division by it on the device (tools/kbench_quantile.py)
+
+
+def quantile_normalise(x):
+    """x / np.quantile(np.abs(x), 0.999) in float32 (reference src/vc_infer_pipeline.py:105-108, 195-196).  A numpy x is served by
+    numpy and returns numpy.  A tensor x (on the device the kernels run on) is served by ops.abs_quantile and ops.div_scalar and
+    never leaves the device: the same bits, which rests on ops.quantile_plan restating numpy 2.x's index arithmetic -- under
+    another numpy the tensor goes through the host and numpy, and comes back as numpy."""
+    if torch.is_tensor(x):
+        if DEVICE_QUANTILE and ops.numpy_quantile_mirrored():
+            x = x.detach().float().contiguous().view(-1)
+            return ops.div_scalar(x, ops.abs_quantile(x, 0.999))
+        x = x.detach().cpu().numpy()
+    x = np.asarray(x).astype(np.float32)
+    return x / np.quantile(np.abs(x), 0.999)
+
+
 def mangio_crepe_f0(net, x, p_len, hop, dither=None, group=None):
-    """VC.get_f0_crepe_computation (reference src/vc_infer_pipeline.py:96-137)."""
-    x = x.astype(np.float32)
-    x = x / np.quantile(np.abs(x), 0.999)
+    """VC.get_f0_crepe_computation (reference src/vc_infer_pipeline.py:96-137).  x: numpy, or a tensor on the device the kernels run on
+    (the scale is then taken there, quantile_normalise)."""
+    x = quantile_normalise(x)
     pitch, bins, post = predict(net, x, hop, 50.0, 1100.0, batch_size=hop * 2, dither=dither, group=group)
     p_len = p_len or x.shape[0] // hop
     source = pitch.cpu().float().numpy()
@@ -178,16 +195,16 @@ def mangio_crepe_f0(net, x, p_len, hop, dither=None, group=None):
     return np.nan_to_num(target)
 
 
-def official_crepe_f0(net, x, hop, fmin=50.0, fmax=1100.0, dither=None, group=None):
+def official_crepe_f0(net, x, hop, fmin=50.0, fmax=1100.0, dither=None, group=None, to_host=True):
     """VC.get_f0_official_crepe_computation (reference src/vc_infer_pipeline.py:139-165):
     f0, pd = torchcrepe.predict(audio, 16000, hop, fmin, fmax, model, batch_size=512, return_periodicity=True);
     pd = torchcrepe.filter.median(pd, 3); f0 = torchcrepe.filter.mean(f0, 3); f0[pd < 0.1] = 0.
     The periodicity is the posterior at the Viterbi-decoded bin (torchcrepe.core.periodicity); both 3-frame filters run in
     ops.filter3 (wave-shuffle neighbours)."""
-    x = np.asarray(x, dtype=np.float32)
+    x = x if torch.is_tensor(x) else np.asarray(x, dtype=np.float32)
     pitch, bins, post = predict(net, x, hop, fmin, fmax, batch_size=512, dither=dither, group=group)
     pd = post.gather(1, bins.view(-1, 1)).view(-1)
     pd = ops.filter3(pd, "median")
     f0 = ops.filter3(pitch, "mean")
     f0 = torch.where(pd < 0.1, torch.zeros_like(f0), f0)
-    return f0.cpu().numpy()
+    return f0.cpu().numpy() if to_host else f0

@@ -1572,6 +1572,92 @@ def medfilt3(f0):
 
 
 # ---------------------------------------------------------------------------------------------------
+# Around the estimators of hybrid[...] / mangio-crepe (csrc/select.hip): the quantile of |x|, the division by it, the nan-median
+# ---------------------------------------------------------------------------------------------------
+NANMEDIAN_MAX_ROWS = 8
+
+
+def numpy_quantile_mirrored():
+    """Whether abs_quantile restates the installed numpy: the index and weight arithmetic below is numpy 2.x's (a Python-float q is
+    cast to the data's float32 before the virtual index is formed; 1.x forms it in float64)."""
+    return np.__version__.split(".")[0] == "2"
+
+
+def abs_select(x, rank_lo, rank_hi):
+    """Elements rank_lo and rank_hi (= rank_lo or rank_lo + 1) of sorted(|x|) -> (2,) float32 on x's device; both NaN when x holds
+    a NaN.  x: 1-D float32, 1 to 2^27 elements (ValueError beyond).  Exact (radix select on the bit patterns), no synchronisation."""
+    assert x.dim() == 1 and x.dtype == torch.float32
+    x = x.contiguous()
+    n = x.numel()
+    _check(x)
+    nbytes = _lib.get().aicg_abs_select_workspace_bytes(n)
+    if nbytes <= 0:
+        raise ValueError("abs_select: %d elements (1 to 2^27 are served)" % n)
+    if not (0 <= rank_lo <= rank_hi < n and rank_hi - rank_lo <= 1):
+        raise ValueError("abs_select: ranks %d, %d of %d elements" % (rank_lo, rank_hi, n))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    out = torch.empty(2, dtype=torch.float32, device=x.device)
+    _call("aicg_abs_select_f32", _ptr(x), n, int(rank_lo), int(rank_hi), _ptr(out), _ptr(ws), _stream(x))
+    return out
+
+
+def quantile_plan(n, q):
+    """(rank_lo, rank_hi, weight) of np.quantile(a, q) (method 'linear') for n float32 values and a Python-float q, from n alone, in
+    numpy 2.x's own arithmetic (numpy/lib/_function_base_impl.py: _quantile, _get_indexes, _get_gamma): q and n - 1 become float32,
+    the virtual index is their float32 product, the lower rank its floor and the weight what is left; at or past the last element
+    both ranks are n - 1 and the weight is index + 1 (harmless: the two values are one)."""
+    if not 0.0 <= q <= 1.0:
+        raise ValueError("Quantiles must be in the range [0, 1]")
+    virtual = np.asanyarray((n - 1) * np.asanyarray(q, dtype=np.float32))
+    previous = np.asanyarray(np.floor(virtual))
+    nxt = np.asanyarray(previous + 1)
+    if virtual >= n - 1:
+        previous, nxt = np.asanyarray(np.float32(-1)), np.asanyarray(np.float32(-1))
+    gamma = np.asanyarray(virtual - previous, dtype=virtual.dtype)
+    return int(previous.astype(np.intp)) % n, int(nxt.astype(np.intp)) % n, np.float32(gamma)
+
+
+def abs_quantile(x, q):
+    """np.quantile(np.abs(x), q) of a 1-D float32 device tensor -> 0-dim float32 tensor on the same device, bit for bit what numpy
+    2.x returns (NaN where numpy gives NaN: a NaN in x, or an infinite neighbour).  The two ranks and the weight come from len(x) on
+    the host (quantile_plan), the two order statistics from abs_select and the interpolation from a kernel that rounds like numpy's
+    _lerp; nothing is synchronised.  Under another major version of numpy the arithmetic of the index may differ: callers that
+    promise numpy's bits ask numpy_quantile_mirrored() and keep the host route otherwise."""
+    lo, hi, t = quantile_plan(x.numel(), float(q))
+    ab = abs_select(x, lo, hi)
+    out = torch.empty((), dtype=torch.float32, device=x.device)
+    _call("aicg_quantile_lerp", _ptr(ab), float(t), _ptr(out), _stream(x))
+    return out
+
+
+def div_scalar(x, s):
+    """x / s for float32 x and a 0-dim float32 tensor s on the same device: IEEE division, numpy's bits (torch.div by a host scalar
+    multiplies by the reciprocal on the device)."""
+    assert x.dtype == torch.float32 and s.dtype == torch.float32 and s.numel() == 1 and s.device == x.device
+    x = x.contiguous()
+    y = torch.empty_like(x)
+    if x.numel():
+        _check(x, s)
+        _call("aicg_div_scalar", _ptr(x), _ptr(s), _ptr(y), x.numel(), _stream(x))
+    return y
+
+
+def nanmedian_rows(stack):
+    """np.nanmedian(stack, axis=0) of a (k, n) float64 tensor, 1 <= k <= 8 (ValueError beyond: the caller joins on the host) ->
+    (n,) float64, the same bits: NaNs ignored, NaN for a column of NaNs, (a + b) / 2 for an even count."""
+    assert stack.dim() == 2 and stack.dtype == torch.float64
+    k, n = stack.shape
+    if not 1 <= k <= NANMEDIAN_MAX_ROWS:
+        raise ValueError("nanmedian_rows: %d rows (1 to %d are served)" % (k, NANMEDIAN_MAX_ROWS))
+    stack = stack.contiguous()
+    out = torch.empty(n, dtype=torch.float64, device=stack.device)
+    if n:
+        _check(stack)
+        _call("aicg_nanmedian_rows", _ptr(stack), k, n, _ptr(out), _stream(stack))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------
 # CREPE helpers
 # ---------------------------------------------------------------------------------------------------
 def frame_normalize(frames):

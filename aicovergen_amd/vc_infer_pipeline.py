@@ -202,6 +202,7 @@ class VC(object):
         injected as `self.model_crepe[model]` (tests / benchmarks use seeded parameters)."""
         from . import crepe
         print("Initiating prediction with a crepe_hop_length of: " + str(hop_length))
+        x = x.to(self.device) if torch.is_tensor(x) else x   # a tensor stays on the device: crepe.quantile_normalise
         return crepe.mangio_crepe_f0(self._crepe(model), x, p_len, hop_length, dither=dither, group=self._f0_group(False))
 
     def _crepe(self, model):
@@ -212,36 +213,56 @@ class VC(object):
             self.model_crepe[model] = crepe.load_crepe(model, self.device)
         return self.model_crepe[model]
 
-    def get_f0_official_crepe_computation(self, x, f0_min, f0_max, model="full", dither=None):
+    def get_f0_official_crepe_computation(self, x, f0_min, f0_max, model="full", dither=None, to_host=True):
         """f0_method 'crepe' / 'crepe-tiny' (reference :139-165): torchcrepe.predict at the 10 ms hop with periodicity, 3-frame
-        median of the periodicity, 3-frame mean of f0, unvoiced (periodicity < 0.1) frames zeroed."""
+        median of the periodicity, 3-frame mean of f0, unvoiced (periodicity < 0.1) frames zeroed.  `to_host=False` (hybrid on a
+        device track): the float32 device tensor instead of numpy."""
         from . import crepe
         return crepe.official_crepe_f0(self._crepe(model), x, self.window, f0_min, f0_max, dither=dither,
-                                       group=self._f0_group(False))
+                                       group=self._f0_group(False), to_host=to_host)
+
+    HYBRID_METHODS = ("crepe", "crepe-tiny", "mangio-crepe", "mangio-crepe-tiny", "dio")
 
     def get_f0_hybrid_computation(self, methods_str, input_audio_path, x, f0_min, f0_max, p_len, filter_radius,
                                   crepe_hop_length, time_step):
-        """hybrid[m1+m2+...] (reference :175-260): nan-median over the listed estimators on the quantile-normalised signal."""
+        """hybrid[m1+m2+...] (reference :175-260): nan-median over the listed estimators on the quantile-normalised signal.
+        A tensor x stays on the device (crepe.quantile_normalise: ops.abs_quantile / ops.div_scalar, numpy's bits; under a numpy other
+        than 2.x it takes the host route); a numpy x is normalised on the host as before.  The `dio` row (reference :235-245) is DIO,
+        StoneMask and the 3-point median of the NORMALISED signal without its first frame; it is computed in full on every rank, the
+        crepe rows shard as they do alone.  Rows that are all device tensors (dio, crepe[-tiny] of a tensor x; at most
+        ops.NANMEDIAN_MAX_ROWS) are joined by ops.nanmedian_rows, anything else by np.nanmedian: the same bits.  Like the reference,
+        estimators of different lengths raise.  -> float64 numpy."""
+        from . import crepe
         methods = methods_str.split("hybrid")[1].replace("[", "").replace("]", "").split("+")
         print("Calculating f0 pitch estimations for methods: %s" % str(methods))
-        x = x.astype(np.float32)
-        x = x / np.quantile(np.abs(x), 0.999)
+        for method in methods:
+            if method not in self.HYBRID_METHODS:
+                raise NotImplementedError("hybrid f0: method %r is not served inside hybrid[...] (supported there: %s; pm runs alone as "
+                                          "f0_method 'pm', harvest is not built for the MI355X yet)" % (method, ", ".join(self.HYBRID_METHODS)))
+        on_device = torch.is_tensor(x)
+        x = crepe.quantile_normalise(x.to(self.device) if on_device else x)
+        on_device = torch.is_tensor(x)
         stack = []
         for method in methods:
             if method in ("crepe", "crepe-tiny"):
-                f0 = self.get_f0_official_crepe_computation(x, f0_min, f0_max, "tiny" if method.endswith("tiny") else "full")[1:]
+                f0 = self.get_f0_official_crepe_computation(x, f0_min, f0_max, "tiny" if method.endswith("tiny") else "full",
+                                                            to_host=not on_device)[1:]
             elif method in ("mangio-crepe", "mangio-crepe-tiny"):
                 f0 = self.get_f0_crepe_computation(x, f0_min, f0_max, p_len, crepe_hop_length,
                                                    "tiny" if method.endswith("tiny") else "full")
             else:
-                raise NotImplementedError("hybrid f0: method %r needs parselmouth / pyworld (supported inside hybrid[...]: "
-                                          "crepe, crepe-tiny, mangio-crepe, mangio-crepe-tiny)" % method)
-            stack.append(np.asarray(f0, dtype=np.float64))
+                f0 = self._dio_track(x, f0_min, f0_max, 10.0)[1:]
+            stack.append(f0.double() if torch.is_tensor(f0) else np.asarray(f0, dtype=np.float64))
         for fc in stack:
             print(len(fc))
         print("Calculating hybrid median f0 from the stack of: %s" % str(methods))
         if len(stack) == 1:
-            return stack[0]
+            return stack[0].cpu().numpy() if torch.is_tensor(stack[0]) else stack[0]
+        if all(torch.is_tensor(f) for f in stack) and len(stack) <= ops.NANMEDIAN_MAX_ROWS:
+            if len(set(len(f) for f in stack)) != 1:
+                raise ValueError("hybrid f0: the estimators gave %s frames" % [len(f) for f in stack])
+            return ops.nanmedian_rows(torch.stack(stack)).cpu().numpy()
+        stack = [f.cpu().numpy() if torch.is_tensor(f) else f for f in stack]
         return np.nanmedian(stack, axis=0)   # like the reference, estimators of different lengths raise here
 
     def get_f0_pm_computation(self, x, f0_min, f0_max, p_len):
@@ -260,11 +281,13 @@ class VC(object):
         """f0_method 'dio' (reference :300-309): pyworld.dio at the 10 ms frame period, pyworld.stonemask, scipy's medfilt(f0, 3) ->
         len(x) // window + 1 frames.  The track stays on the device (ops.world_dio, ops.stonemask, ops.medfilt3); no weights, no
         communication: every rank computes the whole contour."""
+        return self._dio_track(x, f0_min, f0_max, self.window / self.sr * 1000).cpu().numpy()
+
+    def _dio_track(self, x, f0_min, f0_max, frame_period):
+        """DIO, StoneMask, medfilt(3) of x (numpy or tensor) -> float64 device tensor."""
         xd = (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))).to(self.device)
-        frame_period = self.window / self.sr * 1000
         f0 = ops.world_dio(xd, self.sr, frame_period, float(f0_min), float(f0_max))
-        f0 = ops.medfilt3(ops.stonemask(xd, f0, self.sr, frame_period))
-        return f0.cpu().numpy()
+        return ops.medfilt3(ops.stonemask(xd, f0, self.sr, frame_period))
 
     def _f0_group(self, explicit=True):
         """The process group the f0 estimators may communicate over.  Inside pipeline() the ranks of the job cut RMVPE's U-Net
@@ -314,7 +337,7 @@ class VC(object):
         """The estimator's half of get_f0: the untransposed f0 track in Hz (numpy float64), passed through the _estimated_f0 seam.  Nothing
         here depends on the voice: get_f0 goes on with the key shift and the coarse bins, VC.front keeps the track as it is."""
         f0_min, f0_max = 50, 1100
-        def host(a):   # the crepe branches start with host numpy arithmetic (quantile normalisation), like the reference
+        def host(a):   # crepe[-tiny] alone does no quantile: it takes the track from the host, as it always has
             return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
 
         if _raw_f0 is not None:
@@ -322,7 +345,7 @@ class VC(object):
         elif f0_method == "rmvpe":
             f0 = self._rmvpe().infer_from_audio(x, thred=0.03, group=self._rmvpe_group())
         elif f0_method in ("mangio-crepe", "mangio-crepe-tiny"):
-            f0 = self.get_f0_crepe_computation(host(x), f0_min, f0_max, p_len, crepe_hop_length,
+            f0 = self.get_f0_crepe_computation(x, f0_min, f0_max, p_len, crepe_hop_length,
                                                "tiny" if f0_method.endswith("tiny") else "full")
         elif f0_method in ("crepe", "crepe-tiny"):
             f0 = self.get_f0_official_crepe_computation(host(x), f0_min, f0_max, "tiny" if f0_method.endswith("tiny") else "full")
@@ -331,12 +354,12 @@ class VC(object):
         elif f0_method == "dio":
             f0 = self.get_f0_dio_computation(x, f0_min, f0_max)
         elif "hybrid" in f0_method:
-            f0 = self.get_f0_hybrid_computation(f0_method, input_audio_path, host(x), f0_min, f0_max, p_len, filter_radius,
+            f0 = self.get_f0_hybrid_computation(f0_method, input_audio_path, x, f0_min, f0_max, p_len, filter_radius,
                                                 crepe_hop_length, self.window / self.sr * 1000)
         else:
             raise NotImplementedError(
                 "f0_method %r needs pyworld's harvest, which is not built for the MI355X yet "
-                "(supported: rmvpe, pm, dio, mangio-crepe[-tiny], crepe[-tiny], hybrid[...] of the crepe methods)" % f0_method)
+                "(supported: rmvpe, pm, dio, mangio-crepe[-tiny], crepe[-tiny], hybrid[...] of the crepe methods and dio)" % f0_method)
         return np.asarray(self._estimated_f0(0, len(f0), np.asarray(f0, dtype=np.float64)), dtype=np.float64)
 
     def get_f0(self, input_audio_path, x, p_len, f0_up_key, f0_method, filter_radius, crepe_hop_length, inp_f0=None,

@@ -579,6 +579,29 @@ int aicg_stonemask(const float* x, int64_t n, int sample_rate, double frame_peri
                    void* stream);
 int aicg_medfilt3(const double* f0, int64_t n, double* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * What hybrid[...] and mangio-crepe do around the estimators (src/vc_infer_pipeline.py:103-104, 183-184, 253-259): the 0.999 quantile
+ * of |x|, the division by it, the nan-median over the estimators' tracks (csrc/select.hip).  Exact, order-independent.
+ *
+ * aicg_abs_select_workspace_bytes: the byte size of aicg_abs_select_f32's workspace for n elements (the caller owns it; a positive
+ *   return value), AICG_E_SHAPE for n outside [1, 2^27].
+ * aicg_abs_select_f32: out2[0], out2[1] = elements rank_lo and rank_hi (zero-based; rank_hi = rank_lo or rank_lo + 1, AICG_E_ARG
+ *   otherwise) of x's absolute values in ascending order, the order being that of the bit patterns with the sign bit cleared: radix
+ *   select, four passes of eight bits, an LDS histogram per workgroup added to a global one with integer atomics, a one-workgroup
+ *   kernel picking the bucket of each rank.  Any NaN in x makes both NaN.  No host synchronisation; AICG_E_SHAPE for n outside [1, 2^27].
+ * aicg_quantile_lerp: out[0] = numpy's _lerp(ab[0], ab[1], t): a + (b - a) t, and b - (b - a) (1 - t) for t >= 0.5, each operation
+ *   rounded to fp32 on its own.
+ * aicg_div_scalar: y[i] = x[i] / s[0], correctly rounded (s: one fp32 in device memory).  May run in place.
+ * aicg_nanmedian_rows: stack (k, n) float64, 1 <= k <= 8 (AICG_E_SHAPE beyond) -> out (n): per column the median of the non-NaN
+ *   values, (a + b) / 2 of the two middle ones for an even count (an add, then a divide) and of the middle one with itself for an odd
+ *   count, NaN for a column of NaNs: numpy.nanmedian(stack, axis=0).
+ * ---------------------------------------------------------------------------------------------- */
+int aicg_abs_select_workspace_bytes(int64_t n);
+int aicg_abs_select_f32(const float* x, int64_t n, int64_t rank_lo, int64_t rank_hi, float* out2, void* workspace, void* stream);
+int aicg_quantile_lerp(const float* ab, float t, float* out, void* stream);
+int aicg_div_scalar(const float* x, const float* s, float* y, int64_t n, void* stream);
+int aicg_nanmedian_rows(const double* stack, int k, int64_t n, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

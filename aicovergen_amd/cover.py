@@ -310,11 +310,32 @@ def pitch_shift(audio_path, pitch_change):
     return output_path
 
 
+def _write_bytes(path, data):
+    with open(path, "wb") as f:
+        f.write(data.tobytes())
+
+
+def export_flac(pcm, sr, output_path, fetch=None):
+    """(frames, channels) int16 on the device -> a FLAC file, encoded on the device (ops.flac_encode): only the file's bytes are copied
+    to the host (pinned memory, _Fetch) and written as they are.  With `fetch` the copy and the write are queued on it; without, the
+    file exists on return."""
+    mine = fetch is None
+    if mine:
+        fetch = _Fetch(_lib.backend() == "hip")
+    fetch.add(_write_bytes, output_path, ops.flac_encode(pcm, sr))
+    if mine:
+        fetch.flush()
+    return output_path
+
+
 def export(pcm, sr, output_path, output_format):
-    """pydub export: WAV directly; any other format through ffmpeg (`ffmpeg -y -f wav -i <tmp.wav> -f <format> <out>`)."""
+    """pydub export: WAV directly; FLAC through the device encoder (export_flac; ffmpeg installed or not); any other format through
+    ffmpeg (`ffmpeg -y -f wav -i <tmp.wav> -f <format> <out>`)."""
     if output_format == "wav":
         write_pcm16(output_path, pcm, sr)
         return output_path
+    if output_format == "flac":     # never ffmpeg's: one bitstream on every machine (export_flac)
+        return export_flac(torch.from_numpy(np.array(pcm, dtype=np.int16)).to(_device()), sr, output_path)
     ffmpeg = shutil.which("ffmpeg")
     if ffmpeg is None:
         raise RuntimeError("combine_audio: writing %r needs ffmpeg on PATH (only 'wav' is written without it)" % (output_format,))
@@ -334,7 +355,10 @@ def combine_audio(audio_paths, output_path, main_gain, backup_gain, inst_gain, o
     stems = [read_pcm16(p) for p in audio_paths[:3]]
     t = [(torch.from_numpy(np.ascontiguousarray(d)).to(dev), sr) for d, sr in stems]
     out, sr = mix_stems(t[0][0], t[0][1], t[1][0], t[1][1], t[2][0], t[2][1], main_gain, backup_gain, inst_gain)
-    export(out.cpu().numpy(), sr, output_path, output_format)
+    if output_format == "flac":
+        export_flac(out, sr, output_path)
+    else:
+        export(out.cpu().numpy(), sr, output_path, output_format)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -717,7 +741,10 @@ class CoverSession:
             main_stream.wait_stream(side)
             inst, backup = shifted["inst"], shifted["backup"]
         out, sr = mix_stems(mixed, ai_sr, backup, backup_sr, inst, inst_sr, main_gain, backup_gain, inst_gain)
-        fetch.add(lambda p, pcm, r: export(pcm, r, p, output_format), ai_cover_path, out, sr)
+        if output_format == "flac":      # encoded here; the file's bytes are what leaves the device
+            export_flac(out, sr, ai_cover_path, fetch)
+        else:
+            fetch.add(lambda p, pcm, r: export(pcm, r, p, output_format), ai_cover_path, out, sr)
         self._mark("pitch_join_and_mix_s", t0)
         if song is not None and fetch.has_stems:      # stems that this call writes: stamped once their files exist
             flush = fetch.flush
@@ -835,7 +862,7 @@ def build_parser():
     p.add_argument("-rwet", "--reverb-wetness", type=float, default=0.2, help="Reverb wet level between 0 and 1")
     p.add_argument("-rdry", "--reverb-dryness", type=float, default=0.8, help="Reverb dry level between 0 and 1")
     p.add_argument("-rdamp", "--reverb-damping", type=float, default=0.7, help="Reverb damping between 0 and 1")
-    p.add_argument("-oformat", "--output-format", type=str, default="mp3", help="Output format of audio file. mp3 for smaller file size, wav for best quality")
+    p.add_argument("-oformat", "--output-format", type=str, default="mp3", help="Output format of audio file. mp3 for smaller file size, wav for best quality, flac for both (lossless, encoded on the device, needs no ffmpeg)")
     # Not one of main.py's flags.  SUPPRESS keeps it out of the parsed namespace unless given, so a command line of main.py's parses to
     # exactly main.py's namespace (tests/test_cover_pipeline.py compares the two whole); main() reads it with a default of 0.
     p.add_argument("-osr", "--resample-sr", type=int, default=argparse.SUPPRESS, help="Sample rate of the AI vocals (>= 16000); 0 or absent: the voice model's own rate")

@@ -1658,6 +1658,44 @@ def nanmedian_rows(stack):
 
 
 # ---------------------------------------------------------------------------------------------------
+# The cover's file, encoded where the mix lives (csrc/flac.hip)
+# ---------------------------------------------------------------------------------------------------
+FLAC_BLOCKS = (256, 512, 1024, 2048, 4096)
+
+
+def flac_encode(pcm, sr, block=4096):
+    """(frames, channels) int16 PCM, 1 or 2 channels, on the device -> 1-D uint8 tensor on the same device: exactly the bytes of a FLAC
+    file (RFC 9639) that decodes to `pcm`.  "fLaC", one STREAMINFO block and the frames of a fixed-blocksize stream of `block` samples
+    (256, 512, 1024, 2048 or 4096); no seek table and no tags, and STREAMINFO's MD5 field is all zero, which the RFC allows as "not
+    computed".  Subframes: the cheapest by exact bit count of CONSTANT, VERBATIM, FIXED 0-4 and LPC 1-8 with partitioned Rice coding,
+    stereo decorrelation per frame; CRCs on the device.  Zero frames give the 42 header bytes.  The file's size is read back from
+    the device (one 8-byte copy: the call waits for the encoder).  TypeError for another dtype, ValueError for another channel count,
+    block size or sample rate."""
+    if not isinstance(pcm, torch.Tensor) or pcm.dtype != torch.int16:
+        raise TypeError("flac_encode: (frames, channels) int16 PCM expected, found %s" % (getattr(pcm, "dtype", type(pcm)),))
+    if pcm.dim() == 1:
+        pcm = pcm.view(-1, 1)
+    if pcm.dim() != 2 or pcm.shape[1] not in (1, 2):
+        raise ValueError("flac_encode: 1 or 2 channels are encoded, found shape %s" % (tuple(pcm.shape),))
+    if int(block) not in FLAC_BLOCKS:
+        raise ValueError("flac_encode: block size %r (one of %s)" % (block, ", ".join(map(str, FLAC_BLOCKS))))
+    if not 1 <= int(sr) < (1 << 20):
+        raise ValueError("flac_encode: sample rate %r" % (sr,))
+    pcm = pcm.contiguous()
+    n, ch = pcm.shape
+    _check(pcm)
+    geom = torch.zeros(4, dtype=torch.int64)
+    _call("aicg_flac_geometry", n, ch, int(sr), int(block), _ptr(geom))
+    _, ws_bytes, capacity, _ = geom.tolist()
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=pcm.device)
+    out = torch.empty(capacity, dtype=torch.uint8, device=pcm.device)
+    size = torch.zeros(1, dtype=torch.int64, device=pcm.device)
+    _call("aicg_flac_encode", _ptr(pcm), n, ch, int(sr), int(block), _ptr(ws), _ptr(out), capacity, _ptr(size), _stream(pcm))
+    return out[:int(size.item())]
+
+
+
+# ---------------------------------------------------------------------------------------------------
 # CREPE helpers
 # ---------------------------------------------------------------------------------------------------
 def frame_normalize(frames):

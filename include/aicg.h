@@ -602,6 +602,26 @@ int aicg_quantile_lerp(const float* ab, float t, float* out, void* stream);
 int aicg_div_scalar(const float* x, const float* s, float* y, int64_t n, void* stream);
 int aicg_nanmedian_rows(const double* stack, int k, int64_t n, double* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The finished cover as a FLAC file, encoded on the device (RFC 9639; csrc/flac.hip, tests/flac_decode_ref.py).
+ *
+ * aicg_flac_geometry: geom[0..4) = number of frames ceil(n / block), byte size of aicg_flac_encode's workspace, capacity in bytes `out`
+ *   must have (the file cannot be larger), 32-bit words of a subframe slot.  n: samples a channel.  AICG_E_SHAPE for channels
+ *   outside {1, 2} and for n < 0, n >= 2^36 or 2^31 frames and more; AICG_E_ARG for a block size outside {256, 512, 1024, 2048,
+ *   4096} and a sample rate outside [1, 2^20).
+ * aicg_flac_encode: pcm int16 (n, channels) -> out: "fLaC", one STREAMINFO block marked last (min = max block size = block, the
+ *   smallest and largest frame, rate, channels, 16 bits, n; the MD5 field all zero, RFC 9639's "not computed"), then the frames of a
+ *   fixed-blocksize stream; no seek table, no tags.  n_bytes[0] (device memory, int64) = the file's size.  n = 0 gives the 42 header
+ *   bytes.  Per subframe the candidate with the fewest bits by exact count among CONSTANT, VERBATIM, FIXED 0..4 and LPC 1..8 (12-bit
+ *   coefficients; only predictor orders below the block's sample count), residuals in partitioned Rice coding with 4-bit parameters,
+ *   partition orders 0..6, the escape code where it is shorter; a tie goes to the earlier candidate.  Stereo: independent,
+ *   left/side, side/right or mid/side by the exact total.  CRC-8 and CRC-16 computed on the device.  Same input, same bytes.
+ *   Same codes as aicg_flac_geometry; AICG_E_ARG for a null pointer or a capacity below geom[2].  Nothing synchronises.
+ * ---------------------------------------------------------------------------------------------- */
+int aicg_flac_geometry(int64_t n, int channels, int sample_rate, int block, int64_t* geom);
+int aicg_flac_encode(const void* pcm, int64_t n, int channels, int sample_rate, int block, void* workspace, void* out, int64_t capacity,
+                     int64_t* n_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
